@@ -11,6 +11,12 @@ convergence tail -- the last refine rounds of its few slow ZMWs -- overlaps the 
 ZMW thread pool overlaps ZMWs.  Each step's ZMWs are polished as BATCH_SPLIT device batches on S = 8 slots (the
 measured best shape, profiles/r4u_batch_shape.txt), capped by what fits in HBM.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line.  `--full`
+adds the CPU leg after the timed steps: the CPU restatement on a sample of the timed ZMWs (cpu_baseline, vs_cpu)
+and the check of the run's records against it (parity_sample).  `--dump-outputs DIR` writes the records of the
+last timed step's ZMWs as DIR/<field>.npy; with the same arguments the inputs, and so the files, are the same
+from run to run.
+
 Multi-GPU: `--gpus N` without a launcher spawns N ranks itself (one process per GPU, RANK/LOCAL_RANK/
 WORLD_SIZE set before any HIP call; the parent never touches the GPU); under torch.distributed.run the
 launcher's ranks are used.  Each rank polishes its own K steps (weak scaling, no data-path collective);
@@ -71,8 +77,17 @@ def parse():
                          "length/pass buckets, memory-sized batches, largest first); smrtcell: configs[4], a mix "
                          "of the three (steps x zmws-per-step ZMWs in total, strong scaling) pulled by the ranks "
                          "from a dynamic queue.  For the queue workloads the timed region includes the read upload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU leg: the CPU restatement on a sample of the timed "
+                         "ZMWs (cpu_baseline, vs_cpu) and the parity check of the run's records against it "
+                         "(parity_sample; a mismatch exits 3).  A plain run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the records of the last step's ZMWs (what a caller of the "
+                         "timed path receives) as DIR/<field>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="ZMWs polished by the CPU baseline (0 = skip; default 256 for 2kb, 0 otherwise)")
+                    help="with --full: ZMWs polished by the CPU baseline (0 = skip; default 256 for 2kb, 16-32 for "
+                         "the queue workloads)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--streams", type=int, default=0,
                     help="workspace slots = batches polished concurrently (0 = the measured best for the stage, capped by HBM)")
@@ -93,7 +108,9 @@ def parse():
                          "the Quiver family (QV-feature reads, FP32 log-space recursions) through "
                          "pbccs_quiver_polish_batch on configs[1]-shaped ZMWs")
     a = ap.parse_args()
-    if a.one_stream:   # read by the engine when it makes a batch (before any HIP call here)
+    if not a.full:   # the CPU leg (baseline + parity) is a run of its own on the host: --full only
+        a.cpu_sample = 0
+    if a.one_stream:  # read by the engine when it makes a batch (before any HIP call here)
         os.environ["PBCCS_ONE_STREAM"] = "1"
     return a
 
@@ -119,6 +136,105 @@ def emit(out):
 def log(rank, *a):
     if rank == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# synthetic inputs of the headline line, generated by worker processes
+# ---------------------------------------------------------------------------------------------------------
+def _synth_step(task):
+    from pbccs_amd import synth
+    n, length, passes, seed = task
+    return synth.make_zmws(n, length, passes, seed=seed)
+
+
+class StepInputs:
+    """The configs[1] ZMWs of the warmup and timed steps, one seeded synth.make_zmws call per step (the same ZMWs
+    whoever generates them).  A step takes about a second of numpy and string work on one core, so the steps are
+    generated by worker processes on this rank's CPU share, forked before the process imports torch or makes any
+    HIP call (the workers never touch the GPU); steps come back in order, the warmup's first, so the timed
+    steps' generation overlaps the warmup."""
+
+    def __init__(self, args, seed0, world):
+        self.tasks = [(args.zmws_per_step, args.length, args.passes, seed0 + 1000 + w) for w in range(args.warmup)] + \
+                     [(args.zmws_per_step, args.length, args.passes, seed0 + k) for k in range(args.steps)]
+        share = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or len(os.sched_getaffinity(0))
+        workers = max(1, min(share, os.cpu_count() or 1) // max(1, world))
+        workers = min(workers, len(self.tasks))
+        self.pool = None
+        if workers > 1:
+            import multiprocessing
+            self.pool = multiprocessing.get_context("fork").Pool(workers)
+            self.it = self.pool.imap(_synth_step, self.tasks)
+        else:
+            self.it = map(_synth_step, self.tasks)
+
+    def take(self, steps):
+        """The ZMWs of the next `steps` steps, concatenated."""
+        return [z for _ in range(steps) for z in next(self.it)]
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.close()
+            self.pool.join()
+            self.pool = None
+
+
+# ---------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def _dump_row(v):
+    """One record's field as a 1-D array: a string as its byte codes and integers in float32 (all far below 2^24),
+    floats in float64; None when the field does not hold numbers."""
+    import numpy as np
+    if isinstance(v, str):
+        return np.frombuffer(v.encode(), dtype=np.uint8).astype(np.float32)
+    try:
+        a = np.asarray([] if v is None else v)
+    except (ValueError, TypeError):
+        return None
+    if a.dtype.kind not in "biuf":
+        return None
+    return a.astype(np.float64 if a.dtype.kind == "f" and a.size else np.float32).ravel()   # empty: no float seen
+
+
+def dump_outputs(path, recs):
+    """Write the records `recs` (the last timed step's, in input order) as path/<field>.npy, one row per ZMW: a
+    per-ZMW number as a vector (float64), a variable-length field (consensus as byte codes, QVs, per-read results)
+    as a matrix padded with zeros to the longest row.  Every file holds finite numbers only: a field of floats (the
+    z-scores of reads that were not added are NaN) is written with its NaN / +inf / -inf entries as 0, and
+    <field>_nonfinite.npy beside it marks them 1 / 2 / 3 (0 = finite), so nothing of the record is lost.  Beyond
+    DUMP_LIMIT_BYTES a fixed seeded sample of the ZMWs is written; zmw_index.npy holds the rows' indices in the step."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cols = {}
+    for k in (recs[0] if recs else {}):
+        rows = [_dump_row(r.get(k)) for r in recs]
+        if any(a is None for a in rows):
+            continue
+        scalar = all(np.ndim(r.get(k)) == 0 and r.get(k) is not None and not isinstance(r.get(k), str) for r in recs)
+        dt = np.float64 if scalar or any(a.dtype == np.float64 for a in rows) else np.float32
+        floats = any(a.dtype == np.float64 for a in rows)   # the only fields that can hold a non-finite value
+        cols[k] = (rows, scalar, dt, max(1, max(a.shape[0] for a in rows)), floats)
+    row_bytes = 8 + sum(w * (np.dtype(dt).itemsize + (4 if floats else 0)) for _, _, dt, w, floats in cols.values())
+    fit = max(1, (DUMP_LIMIT_BYTES - 4096 * (2 * len(cols) + 1)) // row_bytes)   # 4096: room for each file's header
+    idx = np.arange(len(recs))
+    if len(recs) > fit:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(len(recs), size=fit, replace=False))
+    np.save(os.path.join(path, "zmw_index.npy"), idx.astype(np.float64))
+    for k, (rows, scalar, dt, w, floats) in cols.items():
+        out = np.zeros((len(idx), w), dtype=dt)
+        for row, i in enumerate(idx):
+            out[row, :rows[i].shape[0]] = rows[i]
+        if floats:
+            mark = np.select([np.isnan(out), np.isposinf(out), np.isneginf(out)], [1, 2, 3], 0).astype(np.float32)
+            out[mark != 0] = 0.0
+            np.save(os.path.join(path, f"{k}_nonfinite.npy"), mark[:, 0] if scalar else mark)
+        np.save(os.path.join(path, f"{k}.npy"), out[:, 0] if scalar else out)
+    return {"dir": path, "zmws": int(len(idx)), "of": len(recs), "fields": sorted(cols)}
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -554,7 +670,7 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
-    if args.cpu_sample is None:   # ~10-60 s of the restatement on the box's 16 threads
+    if args.cpu_sample is None:   # --full: ~10-60 s of the restatement on the box's 16 threads
         args.cpu_sample = {"2kb": 256, "10kb": 16, "mixed": 32, "smrtcell": 32}[args.workload]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -565,6 +681,10 @@ def main():
         local = int(os.environ["PBCCS_BENCH_DEVICE"])
     if world != args.gpus:
         log(rank, f"[bench] note: --gpus {args.gpus} but the launcher started {world} rank(s); using {world}")
+    seed0 = args.seed + 7919 * rank
+    inputs = None
+    if args.stage == "polish" and args.workload == "2kb":   # the workers fork here, before torch and HIP
+        inputs = StepInputs(args, seed0, world)
     # torch first: the engine then binds to the same HIP runtime instance (both carry soname libamdhip64.so.7)
     import torch
     import torch.distributed as dist
@@ -575,7 +695,6 @@ def main():
         dist.init_process_group(backend="gloo")   # barrier + max-time + the queue's counter: no device collective
 
     import pbccs_amd
-    from pbccs_amd import synth
 
     def barrier():
         if world > 1:
@@ -593,7 +712,6 @@ def main():
     settings = pbccs_amd.ConsensusSettings()
     if args.batch_zmws and args.workload != "2kb":
         settings.zmws_per_batch = args.batch_zmws
-    seed0 = args.seed + 7919 * rank
 
     if args.stage == "poa":
         return poa_stage(args, rank, world, eng, barrier, sync, seed0)
@@ -604,6 +722,8 @@ def main():
     if args.workload != "2kb":
         job_time, local_time, res, workload, scaling, total, qstats, extra = queue_workload(args, rank, world, eng,
                                                                                             settings, seed0)
+        if args.dump_outputs and rank == 0:
+            log(rank, f"[bench] outputs: {dump_outputs(args.dump_outputs, res[-args.zmws_per_step:])}")
         return report(args, rank, world, eng, slots, job_time, local_time, res, workload, scaling, total, qstats,
                       extra=extra, settings=settings)
 
@@ -621,8 +741,7 @@ def main():
         L.check(L.load().pbccs_polish_batch(eng._h, m._ins, len(m.zmws), ctypes.byref(opts), m._outs))
 
     # ---- warmup (untimed): W steps, concurrently over the slots like the timed ones ------------------
-    wz = [z for w in range(args.warmup)
-          for z in synth.make_zmws(args.zmws_per_step, args.length, args.passes, seed=seed0 + 1000 + w)]
+    wz = inputs.take(args.warmup)
     if wz:
         polish_queue(_Marshalled(wz))
     log(rank, f"[bench] warmup done ({args.warmup} x {args.zmws_per_step} ZMWs over {slots} slots)")
@@ -637,9 +756,8 @@ def main():
     # ---- inputs before the timed region: the synthetic generation (Python strings: the stand-in for reading the
     # subreads) and their marshalling into the C structs of the boundary (the stand-in for the reader's records)
     t_prep = time.perf_counter()
-    zs_all = []
-    for k in range(args.steps):
-        zs_all.extend(synth.make_zmws(args.zmws_per_step, args.length, args.passes, seed=seed0 + k))
+    zs_all = inputs.take(args.steps)
+    inputs.close()
     synth_s = time.perf_counter() - t_prep
     tm = time.perf_counter()
     marshalled = _Marshalled(zs_all)
@@ -667,13 +785,16 @@ def main():
     prep["create_thread_s_in_timed"] = round((c0["create_host_ns"] + c0["create_upload_ns"]) / 1e9, 3)
     prep["create_host_s"] = round(c0["create_host_ns"] / 1e9, 3)
     prep["create_upload_s"] = round(c0["create_upload_ns"] / 1e9, 3)
-    prep["note"] = ("outside the timed region: synth_s the synthetic subreads, marshal_s the boundary's C structs "
+    prep["note"] = ("outside the timed region: synth_s the wait for the synthetic subreads (generated by worker "
+                    "processes since the start of the run), marshal_s the boundary's C structs "
                     "(the reader's part).  Inside it, on the slot threads: pbccs_batch_create per device batch "
                     "(create_host_s the batch's copy of its inputs and the read pool, create_upload_s the "
                     "reservations and the read upload) and the per-ZMW setup of Consensus.h:437-453 (transition "
                     "tables, expectations, reverse-complement template, descriptor arena: derive_thread_s_in_timed)")
     workload = (f"configs[1]: synthetic {args.length} bp insert, {args.passes} full passes, "
                 f"{args.zmws_per_step} ZMWs per step")
+    if args.dump_outputs and rank == 0:
+        log(rank, f"[bench] outputs: {dump_outputs(args.dump_outputs, res[-args.zmws_per_step:])}")
     report(args, rank, world, eng, slots, job_time, local_time, res, workload, "weak", len(res) * world,
            extra={"host": hostu, "zs": zs_all, "costs": None, "prepare": prep}, settings=settings)
 
@@ -767,6 +888,8 @@ def poa_stage(args, rank, world, eng, barrier, sync, seed0):
                 "draft_len_mean": round(sum(len(r["consensus"]) for b in res for r in b) / max(1, total // world), 1)},
     }
     out["host"] = hostu
+    if args.dump_outputs and rank == 0:
+        log(rank, f"[bench] outputs: {dump_outputs(args.dump_outputs, res[-1] if res else [])}")
     parity_ok = True
     if rank == 0 and world == 1 and args.cpu_sample > 0:
         cb, parity = poa_cpu_baseline(args, steps_in, res, min(args.cpu_sample, 48))
@@ -909,6 +1032,8 @@ def quiver_stage(args, rank, world, eng, barrier, sync, seed0):
                            "gcells": round(v["cells"] / 1e9, 4), "gbytes": round(v["bytes"] / 1e9, 4)}
                        for k, v in stats.items() if v["launches"]},
            "host": hostu}
+    if args.dump_outputs and rank == 0:
+        log(rank, f"[bench] outputs: {dump_outputs(args.dump_outputs, res[-args.zmws_per_step:])}")
     parity_ok = True
     if rank == 0 and args.cpu_sample:
         cb, parity = quiver_cpu_baseline(args, zs, res)
@@ -1059,6 +1184,8 @@ def ccs_stage(args, rank, world, eng, slots, settings, barrier, sync, seed0):
         out["kernels"] = {k: {"launches": v["launches"], "device_ms": round(v["device_ms"], 3),
                               "gcells": round(v["cells"] / 1e9, 4), "gbytes": round(v["bytes"] / 1e9, 4)}
                           for k, v in kstats.items() if v["launches"]}
+    if args.dump_outputs and rank == 0:
+        log(rank, f"[bench] outputs: {dump_outputs(args.dump_outputs, res[-args.zmws_per_step:])}")
     parity_ok = True
     if rank == 0 and world == 1 and args.cpu_sample > 0:
         cb, parity = ccs_cpu_baseline(args, settings, work, res, min(args.cpu_sample, 160))

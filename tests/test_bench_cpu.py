@@ -106,7 +106,9 @@ def test_cpu_leg_checks_the_timed_records_and_fails_on_a_mismatch():
     costs = [bench.zmw_cost(z) for z in zs]
     cb, par = bench.sampled_cpu_baseline(_args(cpu_sample=3), settings, zs, recs, idx, costs)
     ex = cb["extrapolated"]
-    assert par["ok"] and abs(cb["value"] - 2 / ex["core_s_per_zmw"]) < 0.02 * cb["value"]
+    # value = cores / core_s_per_zmw; the line records core_s_per_zmw rounded to 3 decimals (half a unit: 0.0005 s,
+    # which on a fast host is more than 2% of these small ZMWs' ~0.02 s) and value to 4
+    assert par["ok"] and abs(2 / cb["value"] - ex["core_s_per_zmw"]) <= 0.0005 + 1e-6
 
 
 def test_occupancy_report_from_wave_stamps():
@@ -153,3 +155,74 @@ def test_cpu_leg_sample_is_stratified_and_the_power_law_recovers_its_exponent():
     a, alpha = bench.power_law_fit([costs[i] for i in idx], secs)
     assert abs(alpha - 1.3) < 1e-9
     assert bench.power_law_fit([1.0, 1.0, 1.0], [1.0, 2.0, 3.0]) is None
+
+
+def test_plain_run_skips_the_cpu_leg_and_full_keeps_it(monkeypatch):
+    """Without --full the CPU leg (baseline + parity) is off whatever --cpu-sample says; with it the sample size
+    is the option's, or the workload's default."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.cpu_sample == 0 and not a.full and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--cpu-sample", "8"])
+    assert bench.parse().cpu_sample == 0
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--cpu-sample", "8", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.cpu_sample == 8 and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().cpu_sample is None   # main() fills in the workload's default
+
+
+def test_step_inputs_are_the_seeded_steps_in_order():
+    """The worker processes return exactly synth.make_zmws of each step's seed: warmup steps (seed0 + 1000 + w)
+    first, then the timed ones (seed0 + k)."""
+    sys.path.insert(0, ROOT)
+    import argparse
+    import bench
+    from pbccs_amd import synth
+    a = argparse.Namespace(zmws_per_step=5, length=120, passes=3, warmup=2, steps=3)
+    si = bench.StepInputs(a, 11, 1)
+    try:
+        warm, timed = si.take(2), si.take(3)
+    finally:
+        si.close()
+    assert warm == [z for w in range(2) for z in synth.make_zmws(5, 120, 3, seed=1011 + w)]
+    assert timed == [z for k in range(3) for z in synth.make_zmws(5, 120, 3, seed=11 + k)]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per numeric field, float32 / float64, variable-length rows zero-padded; beyond the
+    size limit the same seeded sample of the ZMWs on every run, named by zmw_index.npy."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    recs = [{"status": "Success", "status_code": 0, "consensus": "ACGT" * i, "qvs": [i] * (4 * i),
+             "zscores": [0.5, -1.5][:i % 3], "zg": 1.25 * i, "n_tested": 7 + i, "opaque": {"a": 1}} for i in range(1, 41)]
+    info = bench.dump_outputs(str(tmp_path / "a"), recs)
+    assert info["zmws"] == 40 and "opaque" not in info["fields"]
+    load = lambda d, k: np.load(str(tmp_path / d / (k + ".npy")))
+    cons, qvs, zg, nt = load("a", "consensus"), load("a", "qvs"), load("a", "zg"), load("a", "n_tested")
+    assert cons.dtype == np.float32 and cons.shape == (40, 160) and qvs.shape == (40, 160)
+    assert bytes(cons[2, :12].astype(np.uint8)).decode() == "ACGT" * 3 and not cons[2, 12:].any()
+    assert zg.dtype == np.float64 and zg.shape == (40,) and zg[3] == 5.0 and nt[0] == 8
+    assert load("a", "zscores").dtype == np.float64 and load("a", "zscores").shape == (40, 2)
+    assert list(load("a", "zmw_index")) == list(range(40))
+    bench.dump_outputs(str(tmp_path / "e"), [{"qvs": []}, {"qvs": [3, 4]}])   # an empty row does not widen the type
+    assert load("e", "qvs").dtype == np.float32 and load("e", "qvs").tolist() == [[0, 0], [3, 4]]
+    # every file is finite: NaN / +inf / -inf of a float field are written as 0 and marked 1 / 2 / 3 beside it
+    nan, inf = float("nan"), float("inf")
+    bench.dump_outputs(str(tmp_path / "n"), [{"zscores": [nan, 1.5, inf], "zg": nan}, {"zscores": [-inf], "zg": 2.0}])
+    assert load("n", "zscores").tolist() == [[0, 1.5, 0], [0, 0, 0]] and load("n", "zg").tolist() == [0, 2.0]
+    assert load("n", "zscores_nonfinite").tolist() == [[1, 0, 2], [3, 0, 0]] and load("n", "zg_nonfinite").tolist() == [1, 0]
+    for d in ("a", "n"):
+        assert all(np.isfinite(np.load(str(tmp_path / d / f))).all() for f in os.listdir(str(tmp_path / d)))
+    assert not load("a", "zscores_nonfinite").any() and load("a", "zscores_nonfinite").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    bench.dump_outputs(str(tmp_path / "b"), recs)
+    bench.dump_outputs(str(tmp_path / "c"), recs)
+    idx = load("b", "zmw_index").astype(int)
+    assert 0 < len(idx) < 40 and list(idx) == sorted(set(idx)) and list(idx) == list(load("c", "zmw_index").astype(int))
+    assert (load("b", "consensus") == cons[idx]).all() and (load("b", "zg") == zg[idx]).all()
+    total = sum(os.path.getsize(os.path.join(str(tmp_path / "b"), f)) for f in os.listdir(str(tmp_path / "b")))
+    assert total <= 64 << 10

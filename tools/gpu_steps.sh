@@ -44,11 +44,13 @@ step() {
         cp "$(find $OUT/apiccs -name '*hip_api_stats.csv' | head -1)" $OUT/ccs_hip_api_stats.csv && \
         grep -E "hipDeviceSynchronize|hipFree\"|hipMalloc\"|hipStreamSynchronize|hipMemcpyAsync" $OUT/ccs_hip_api_stats.csv | cut -c1-120 ;;
     bench2r)  # the headline on two self-launched ranks pinned to the one device (a rehearsal of --gpus N)
-      PBCCS_BENCH_DEVICE=0 timeout -k 10 400 $BENCH --gpus 2 --steps 4 --warmup 1 --streams 4 > $OUT/bench_2ranks.json \
+      PBCCS_BENCH_DEVICE=0 timeout -k 10 400 $BENCH --full --gpus 2 --steps 4 --warmup 1 --streams 4 > $OUT/bench_2ranks.json \
         2> $OUT/bench_2ranks.err && summ $OUT/bench_2ranks.json && \
         python3 -c "import json; d=json.load(open('$OUT/bench_2ranks.json')); print(d['n_gpus'], d['scaling'], d.get('parity_sample', {}).get('ok'))" ;;
-    bench)    # the driver's command
-      timeout -k 10 400 $BENCH --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err && summ $OUT/bench.json ;;
+    bench)    # the driver's command with the CPU leg (cpu_baseline, vs_cpu, parity_sample)
+      timeout -k 10 400 $BENCH --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err && summ $OUT/bench.json ;;
+    benchplain) # the driver's command as the driver runs it
+      timeout -k 10 400 $BENCH --gpus 1 --steps 20 --warmup 5 > $OUT/bench_plain.json 2> $OUT/bench_plain.err && summ $OUT/bench_plain.json ;;
     bench5)
       timeout -k 10 300 $BENCH --steps 5 --warmup 1 --cpu-sample 0 > $OUT/bench5.json 2> $OUT/bench5.err && summ $OUT/bench5.json ;;
     prof)     # rocprofv3 kernel summary of the driver's command
@@ -70,13 +72,13 @@ step() {
       PBCCS_ROUND_TRACE=1 PBCCS_FILL_PATHS=1 timeout -k 10 300 $BENCH --streams 1 --steps 5 --warmup 1 --cpu-sample 0 \
         > $OUT/trace1.json 2> $OUT/trace1.err && summ $OUT/trace1.json ;;
     quiver)
-      PBCCS_QUIVER_TRACE=1 timeout -k 10 300 $BENCH --stage quiver --steps 5 --warmup 2 > $OUT/quiver.json 2> $OUT/quiver.err && \
+      PBCCS_QUIVER_TRACE=1 timeout -k 10 300 $BENCH --full --stage quiver --steps 5 --warmup 2 > $OUT/quiver.json 2> $OUT/quiver.err && \
         python3 -c "import json; d=json.load(open('$OUT/quiver.json')); print('quiver', d['value'], 'warmup_call_ms', d.get('warmup_call_ms'), 'timed_call_ms', d.get('timed_call_ms'))" ;;
     poa)
-      timeout -k 10 400 $BENCH --stage poa --steps 5 --warmup 1 > $OUT/poa.json 2> $OUT/poa.err && \
+      timeout -k 10 400 $BENCH --full --stage poa --steps 5 --warmup 1 > $OUT/poa.json 2> $OUT/poa.err && \
         python3 -c "import json; d=json.load(open('$OUT/poa.json')); print('poa', d['value'])" ;;
     ccs)
-      PBCCS_CCS_TRACE=1 timeout -k 10 500 $BENCH --stage ccs --steps 5 --warmup 1 > $OUT/ccs.json 2> $OUT/ccs.err && \
+      PBCCS_CCS_TRACE=1 timeout -k 10 500 $BENCH --full --stage ccs --steps 5 --warmup 1 > $OUT/ccs.json 2> $OUT/ccs.err && \
         python3 -c "import json; d=json.load(open('$OUT/ccs.json')); print('ccs', d['value'], d['zmw_status'])" ;;
     prof10k)  # configs[2] at 2000 ZMWs through the work queue, rocprofv3 kernel summary
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof10k -o run -- $BENCH --workload 10kb \
@@ -84,17 +86,17 @@ step() {
         summ $OUT/bench_10kb.json && \
         cp "$(find $OUT/prof10k -name '*kernel_stats.csv' | head -1)" $OUT/10kb_kernel_stats.csv ;;
     bench10k) # configs[2] at ZMWS10K ZMWs (default 10000), no profiler, progress on stderr
-      timeout -k 10 1000 $BENCH --workload 10kb --steps 1 --zmws-per-step ${ZMWS10K:-10000} --warmup 0 \
+      timeout -k 10 1000 $BENCH --full --workload 10kb --steps 1 --zmws-per-step ${ZMWS10K:-10000} --warmup 0 \
         > $OUT/bench_10kb_big.json 2> $OUT/bench_10kb_big.err && summ $OUT/bench_10kb_big.json ;;
     mixed)    # configs[3] at 2000 ZMWs
-      timeout -k 10 900 $BENCH --workload mixed --steps 1 --zmws-per-step 2000 --warmup 0 > $OUT/bench_mixed.json \
+      timeout -k 10 900 $BENCH --full --workload mixed --steps 1 --zmws-per-step 2000 --warmup 0 > $OUT/bench_mixed.json \
         2> $OUT/bench_mixed.err && summ $OUT/bench_mixed.json ;;
     abmixed)  # configs[3] at MIXN ZMWs under each "VAR=x VAR2=y" variant of VARIANTS (";"-separated), no profiler
       local k=0
       IFS=';' read -ra VS <<< "${VARIANTS:-NONE=1}"
       for v in "${VS[@]}"; do
         k=$((k+1))
-        ( eval "export $v"; timeout -k 10 600 $BENCH --workload mixed --steps 1 --zmws-per-step ${MIXN:-1000} --warmup 0 \
+        ( eval "export $v"; timeout -k 10 600 $BENCH --full --workload mixed --steps 1 --zmws-per-step ${MIXN:-1000} --warmup 0 \
           --streams ${MIXSTREAMS:-8} ${MIXARGS:-} ) > $OUT/abmixed_$k.json 2> $OUT/abmixed_$k.err || \
           { echo "variant $k ($v) failed"; tail -3 $OUT/abmixed_$k.err; return 1; }
         echo "[$v] $(summ $OUT/abmixed_$k.json) $(python3 -c "import json; d=json.load(open('$OUT/abmixed_$k.json')); print('polished', d['polished'], 'parity', d.get('parity_sample', {}).get('ok'))")"
@@ -106,12 +108,12 @@ step() {
         python3 tools/api_gaps.py "$(find $OUT/apimixed -name '*hip_api_trace.csv' | head -1)" 200 > $OUT/api_gaps.json && \
         head -60 $OUT/api_gaps.json && rm -f "$(find $OUT/apimixed -name '*hip_api_trace.csv' | head -1)" ;;
     profmixed) # configs[3] at 2000 ZMWs on 8 slots under rocprofv3 (the line and its kernel summary in one run)
-      timeout -k 10 1000 rocprofv3 --kernel-trace --stats -f csv -d $OUT/profmixed -o run -- $BENCH --workload mixed \
+      timeout -k 10 1000 rocprofv3 --kernel-trace --stats -f csv -d $OUT/profmixed -o run -- $BENCH --full --workload mixed \
         --steps 1 --zmws-per-step 2000 --warmup 0 --streams 8 > $OUT/bench_mixed.json 2> $OUT/bench_mixed.err && \
         summ $OUT/bench_mixed.json && \
         cp "$(find $OUT/profmixed -name '*kernel_stats.csv' | head -1)" $OUT/mixed_kernel_stats.csv ;;
     cell2)    # configs[4]: two ranks sharing the one device (a rehearsal of the multi-rank queue), CELLN ZMWs
-      PBCCS_BENCH_DEVICE=0 timeout -k 10 ${CELLTO:-1000} $BENCH --gpus 2 --workload smrtcell --steps 1 \
+      PBCCS_BENCH_DEVICE=0 timeout -k 10 ${CELLTO:-1000} $BENCH --full --gpus 2 --workload smrtcell --steps 1 \
         --zmws-per-step ${CELLN:-10000} --warmup 0 --streams 4 > $OUT/bench_cell2.json 2> $OUT/bench_cell2.err && \
         summ $OUT/bench_cell2.json ;;
     ab_tall)  # interleaved A/B of the tall fill's layout: "G:rows" (PBCCS_TALL_G, PBCCS_TALL_ROWS), 10 steps each
