@@ -328,6 +328,69 @@ int pbccs_quiver_refine_consensus(pbccs_quiver_scorer* s, const pbccs_refine_opt
                                   long long* n_applied, int* converged);
 int pbccs_quiver_consensus_qvs(pbccs_quiver_scorer* s, int* qvs, int cap, int* n);
 
+/* ---- Quiver: mutations of any width ---------------------------------------------------------------
+ * Mutation (Mutation.hpp) with its new-bases string: an insertion has start == end and n_bases >= 1, a
+ * deletion start < end and n_bases == 0, a substitution n_bases == end - start (Mutation-inl.hpp:102-115).
+ * Bases are A, C, G, T and the reference's phony test bases M and N, complements of each other
+ * (Sequence.cpp:41-78).  n_bases <= 7: the reference's extend buffer has 8 columns (EXTEND_BUFFER_COLUMNS,
+ * asserted at Quiver/MutationScorer.cpp:177).  The Arrow scorer takes single-base mutations only, as the
+ * reference's does (Arrow/MutationScorer.cpp:181-183). */
+typedef struct {
+    int type;
+    int start;
+    int end;
+    const char* new_bases; /* n_bases characters (need not be NUL-terminated); ignored for deletions */
+    int n_bases;
+} pbccs_mutation_ex;
+#define PBCCS_MAX_MUTATION_BASES 7
+
+/* The single-base entry points' twins.  A (read, mutation) pair whose ScoreMutation would need more than 8
+ * extend-buffer columns -- the begin / end cases of Quiver/MutationScorer.cpp:187-220, the whole fill of a
+ * window of 7 or more columns, or an insertion of n bases needing 1 + n -- is found on the host from the
+ * oriented mutation and the read's window before anything is launched: the call returns PBCCS_EINVAL and
+ * computes nothing (the reference writes past its buffer there). */
+int pbccs_quiver_scorer_score_many_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int n, int fast,
+                                      float* scores);
+int pbccs_quiver_scorer_scores_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, float unscored,
+                                  float* per_read);
+int pbccs_quiver_scorer_is_favorable_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int fast,
+                                        int* favorable);
+int pbccs_quiver_scorer_read_score_mutation_ex(pbccs_quiver_scorer* s, int i, const pbccs_mutation_ex* m,
+                                               float* score);
+/* ApplyMutations (Mutation.cpp:115-128) with the reads' windows remapped by TargetToQueryPositions; A, C, G
+ * and T only, so the template stays ACGT. */
+int pbccs_quiver_scorer_apply_mutations_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int n);
+
+/* RefineRepeats (Consensus.hpp:69-76): AbstractRefineConsensus (Consensus-inl.hpp:159-251) over
+ * RepeatMutationEnumerator(repeat_length, min_repeat_elements).  The reference's RefineRepeatOptions sets
+ * MaximumIterations = 1 and leaves MutationSeparation and MutationNeighborhood unset (Consensus-inl.hpp:57-68),
+ * and its RefineRepeats body cannot be instantiated, so no reference run of the loop exists: the defaults
+ * here for the two unset fields are DefaultRefineOptions' 10 and 20.  opts NULL = {2, 3, 1, 10, 20}.
+ * repeat_length <= 7 (an insertion of one element needs 1 + repeat_length columns); a candidate that breaks
+ * the 8-column rule ends the call with PBCCS_EINVAL. */
+typedef struct {
+    int repeat_length;
+    int min_repeat_elements;  /* 3 */
+    int max_iterations;       /* 1 */
+    int mutation_separation;  /* 10 */
+    int mutation_neighborhood; /* 20 */
+} pbccs_repeat_options;
+int pbccs_quiver_refine_repeats(pbccs_quiver_scorer* s, const pbccs_repeat_options* opts, long long* n_tested,
+                                long long* n_applied, int* converged);
+
+/* Host-only (no engine or device needed).
+ * pbccs_repeat_mutations: RepeatMutationEnumerator::Mutations(begin, end) (MutationEnumerator.cpp:161-218) in
+ * the reference's order: per repeat run the insertion, then the deletion, of one element.  new_bases of an
+ * insertion points into tpl.  Nothing for min_repeat_elements <= 0 or repeat_length > 31.  *n = the count;
+ * PBCCS_ERANGE when it exceeds cap (out may be NULL with cap 0 to size the call).
+ * pbccs_apply_mutations: ApplyMutations (Mutation.cpp:115-128) into out (NUL-terminated, cap bytes) and
+ * TargetToQueryPositions (Mutation.cpp:193-197) into mtp[tpl_len + 1] (may be NULL).  Any bases; overlapping
+ * edits and edits outside the template are PBCCS_EINVAL. */
+int pbccs_repeat_mutations(const char* tpl, int tpl_len, int repeat_length, int min_repeat_elements, int begin,
+                           int end, pbccs_mutation_ex* out, int cap, int* n);
+int pbccs_apply_mutations(const char* tpl, int tpl_len, const pbccs_mutation_ex* muts, int n, char* out, int cap,
+                          int* len, int* mtp);
+
 /* QvEvaluator (Quiver/QvEvaluator.hpp:90-317): the four move scores of one read (QvSequenceFeatures,
  * Features.hpp:69-100) against a template under QvModelParams, at n cells (i[k], j[k]), evaluated on the device
  * with the recursions' own evaluator.  Inc(i, j) (:160-167), Del(i, j) with the pinStart / pinEnd rule (:169-184),
@@ -388,6 +451,16 @@ typedef struct {
 int pbccs_quiver_polish_batch(pbccs_engine* eng, const pbccs_quiver_config* configs, const char* const* chemistries,
                               int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
                               pbccs_quiver_result* out);
+/* The same with RefineRepeats between RefineConsensus and ConsensusQVs: per ZMW RefineConsensus(opts),
+ * RefineRepeats(repeats), ConsensusQVs, the repeat rounds in lock-step too (one scoring launch series for all
+ * scorers, one reduction and one refill per round; BestSubset on the host).  repeat_tested / repeat_applied
+ * (n entries each, may be NULL) receive RefineRepeats' counts; n_tested / n_applied stay RefineConsensus'.
+ * ok = 0 also where RefineRepeats ended with PBCCS_EINVAL.  repeats == NULL is exactly
+ * pbccs_quiver_polish_batch. */
+int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* configs, const char* const* chemistries,
+                                 int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
+                                 const pbccs_repeat_options* repeats, long long* repeat_tested,
+                                 long long* repeat_applied, pbccs_quiver_result* out);
 
 /* ---- POA draft (pbccs src/SparsePoa.cpp, ConsensusCore/src/C++/Poa) ---------------------------------
  * The read-vs-graph DP and its traceback run on the device (k_poa_fill / k_poa_trace); the graph lives on

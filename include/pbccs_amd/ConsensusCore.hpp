@@ -103,6 +103,22 @@ public:
     {
         return start_ == o.start_ && end_ == o.end_ && type_ == o.type_ && newBases_ == o.newBases_;
     }
+    // one base wide: the single-base ABI (pbccs_mutation) carries it
+    bool IsSingleBase() const
+    {
+        return newBases_.size() <= 1 && end_ - start_ == (type_ == INSERTION ? 0 : 1);
+    }
+    // any width (Quiver's _ex entry points); new_bases points into this Mutation
+    pbccs_mutation_ex ToCEx() const
+    {
+        pbccs_mutation_ex m;
+        m.type = (int)type_;
+        m.start = start_;
+        m.end = end_;
+        m.new_bases = newBases_.data();
+        m.n_bases = (int)newBases_.size();
+        return m;
+    }
     pbccs_mutation ToC() const
     {
         if (newBases_.size() > 1) throw InvalidInputError("Only mutations of size 1 allowed");

@@ -12,6 +12,9 @@
 //   AbstractMultiReadMutationScorer, MultiReadMutationScorer<R>,
 //   SparseSseQv(SumProduct)MultiReadMutationScorer                        Quiver/MultiReadMutationScorer.hpp:55-245
 //   RefineConsensus / ConsensusQVs over a Quiver scorer                    Consensus.hpp:63-79
+//   RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator         MutationEnumerator.hpp:100-129
+//   RefineRepeats / RefineDinucleotideRepeats                              Consensus.hpp:69-76
+// The scorer's Mutation overloads carry mutations of any width (at most 7 new bases) to the engine.
 // BandingOptions here is ConsensusCore::BandingOptions (Quiver's); Arrow's is ConsensusCore::Arrow::BandingOptions,
 // as in the reference.
 #pragma once
@@ -383,6 +386,14 @@ public:
     }
     void ApplyMutations(const std::vector<Mutation>& muts) override
     {
+        bool wide = false;
+        for (const Mutation& m : muts) wide = wide || !m.IsSingleBase();
+        if (wide) {   // mutations of any width (Mutation.cpp:115-128)
+            std::vector<pbccs_mutation_ex> x;
+            for (const Mutation& m : muts) x.push_back(m.ToCEx());
+            detail::Check(pbccs_quiver_scorer_apply_mutations_ex(handle_, x.data(), (int)x.size()));
+            return;
+        }
         std::vector<pbccs_mutation> c;
         for (const Mutation& m : muts) c.push_back(m.ToC());
         detail::Check(pbccs_quiver_scorer_apply_mutations(handle_, c.data(), (int)c.size()));
@@ -402,8 +413,13 @@ public:
     float FastScore(const Mutation& m) const override { return ScoreOne(m, true); }
     std::vector<float> Scores(const Mutation& m, float unscoredValue) const override
     {
-        const pbccs_mutation c = m.ToC();
         std::vector<float> out(NumReads());
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_quiver_scorer_scores_ex(handle_, &x, unscoredValue, out.data()));
+            return out;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_quiver_scorer_scores(handle_, &c, unscoredValue, out.data()));
         return out;
     }
@@ -457,8 +473,13 @@ public:
     // (Quiver/MutationScorer.cpp:113-226), the mutation in the read's window coordinates
     float ReadScoreMutation(int i, const Mutation& m) const override
     {
-        const pbccs_mutation c = m.ToC();
         float v = 0.0f;
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_quiver_scorer_read_score_mutation_ex(handle_, i, &x, &v));
+            return v;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_quiver_scorer_read_score_mutation(handle_, i, &c, &v));
         return v;
     }
@@ -478,15 +499,25 @@ public:
 private:
     float ScoreOne(const Mutation& m, bool fast) const
     {
-        const pbccs_mutation c = m.ToC();
         float v = 0.0f;
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_quiver_scorer_score_many_ex(handle_, &x, 1, fast ? 1 : 0, &v));
+            return v;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_quiver_scorer_score_many(handle_, &c, 1, fast ? 1 : 0, &v));
         return v;
     }
     bool Favorable(const Mutation& m, bool fast) const
     {
-        const pbccs_mutation c = m.ToC();
         int f = 0;
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_quiver_scorer_is_favorable_ex(handle_, &x, fast ? 1 : 0, &f));
+            return f != 0;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_quiver_scorer_is_favorable(handle_, &c, fast ? 1 : 0, &f));
         return f != 0;
     }
@@ -510,6 +541,63 @@ inline bool RefineConsensus(AbstractMultiReadMutationScorer& mms, size_t* nTeste
     *nTested += (size_t)nt;
     *nApplied += (size_t)na;
     return conv != 0;
+}
+
+// RepeatMutationEnumerator / DinucleotideRepeatMutationEnumerator (MutationEnumerator.hpp:100-129,
+// MutationEnumerator.cpp:148-224): host only
+class RepeatMutationEnumerator {
+public:
+    RepeatMutationEnumerator(const std::string& tpl, int repeatLength, int minRepeatElements)
+        : tpl_(tpl), repeatLength_(repeatLength), minRepeatElements_(minRepeatElements)
+    {}
+    std::vector<Mutation> Mutations() const { return Mutations(0, (int)tpl_.size()); }
+    std::vector<Mutation> Mutations(int beginPos, int endPos) const
+    {
+        std::vector<pbccs_mutation_ex> c(2 * tpl_.size() + 2);
+        int n = 0;
+        detail::Check(pbccs_repeat_mutations(tpl_.data(), (int)tpl_.size(), repeatLength_, minRepeatElements_, beginPos,
+                                             endPos, c.data(), (int)c.size(), &n));
+        std::vector<Mutation> out;
+        for (int k = 0; k < n; ++k)
+            out.push_back(Mutation((MutationType)c[k].type, c[k].start, c[k].end,
+                                   c[k].n_bases ? std::string(c[k].new_bases, c[k].n_bases) : std::string()));
+        return out;
+    }
+
+private:
+    std::string tpl_;
+    int repeatLength_, minRepeatElements_;
+};
+
+class DinucleotideRepeatMutationEnumerator : public RepeatMutationEnumerator {
+public:
+    DinucleotideRepeatMutationEnumerator(const std::string& tpl, int minDinucRepeatElements = 3)
+        : RepeatMutationEnumerator(tpl, 2, minDinucRepeatElements)
+    {}
+};
+
+// RefineRepeats / RefineDinucleotideRepeats (Consensus.hpp:69-76).  RefineRepeatOptions (Consensus-inl.hpp:57-68)
+// sets MaximumIterations = 1 and leaves the other two fields unset; DefaultRefineOptions' 10 and 20 stand in.
+inline bool RefineRepeats(AbstractMultiReadMutationScorer& mms, int repeatLength, int minRepeatElements = 3,
+                          size_t* nTested = nullptr, size_t* nApplied = nullptr, int maximumIterations = 1)
+{
+    pbccs_repeat_options o;
+    o.repeat_length = repeatLength;
+    o.min_repeat_elements = minRepeatElements;
+    o.max_iterations = maximumIterations;
+    o.mutation_separation = DefaultRefineOptions.MutationSeparation;
+    o.mutation_neighborhood = DefaultRefineOptions.MutationNeighborhood;
+    long long nt = 0, na = 0;
+    int conv = 0;
+    detail::Check(pbccs_quiver_refine_repeats(mms.Handle(), &o, &nt, &na, &conv));
+    if (nTested) *nTested += (size_t)nt;
+    if (nApplied) *nApplied += (size_t)na;
+    return conv != 0;
+}
+
+inline bool RefineDinucleotideRepeats(AbstractMultiReadMutationScorer& mms, int minDinucleotideRepeatElements = 3)
+{
+    return RefineRepeats(mms, 2, minDinucleotideRepeatElements);
 }
 
 inline std::vector<int> ConsensusQVs(AbstractMultiReadMutationScorer& mms)

@@ -28,25 +28,54 @@ DBL_MAX = 1.7976931348623157e308
 
 
 class Mutation:
-    """ConsensusCore::Mutation for single-base edits (Mutation.hpp:56-129)."""
+    """ConsensusCore::Mutation (Mutation.hpp:56-129).  Mutation(type, position, base) is the single-base form;
+    a multi-character `base` string or an `end` gives a mutation of any width (Mutation-inl.hpp:53-77): an
+    insertion of the string at `position`, a substitution of [position, position + len(base)), a deletion of
+    [position, end).  Multi-base mutations are a Quiver feature: the Arrow scorer refuses them, as the
+    reference's does (Arrow/MutationScorer.cpp:181-183)."""
 
     __slots__ = ("type", "start", "end", "new_base")
 
-    def __init__(self, mtype, position, base="-"):
+    def __init__(self, mtype, position, base="-", end=None):
         self.type = mtype
         self.start = position
-        self.end = position if mtype == INSERTION else position + 1
+        width = 1 if mtype == DELETION else max(1, len(base))
+        if end is not None:
+            self.end = end
+        else:
+            self.end = position if mtype == INSERTION else position + width
         self.new_base = "-" if mtype == DELETION else base
 
+    @property
+    def new_bases(self):
+        return "" if self.type == DELETION else self.new_base
+
+    def is_single_base(self):
+        return len(self.new_base) == 1 and self.end - self.start == (0 if self.type == INSERTION else 1)
+
+    def LengthDiff(self):
+        return len(self.new_bases) if self.type == INSERTION else (self.start - self.end if self.type == DELETION else 0)
+
     def _c(self):
+        if not self.is_single_base():
+            raise _lib_mod.PbccsError(-1, "multi-base mutations are scored by the Quiver scorer only")
         return _lib_mod.CMutation(self.type, self.start, self.end, self.new_base.encode()[:1] or b"-")
+
+    def _cx(self):
+        b = self.new_bases.encode()
+        return _lib_mod.CMutationEx(self.type, self.start, self.end, b, len(b))
 
     def __repr__(self):
         name = ["Insertion", "Deletion", "Substitution"][self.type]
-        return f"{name}({self.new_base})@{self.start}"
+        if self.is_single_base():
+            return f"{name}({self.new_base})@{self.start}"
+        return f"{name}({self.new_bases})@{self.start}:{self.end}"
 
     def __eq__(self, o):
         return (self.type, self.start, self.end, self.new_base) == (o.type, o.start, o.end, o.new_base)
+
+    def __lt__(self, o):   # Mutation-inl.hpp:179-186
+        return (self.start, self.end, self.type, self.new_bases) < (o.start, o.end, o.type, o.new_bases)
 
     def __hash__(self):
         return hash((self.type, self.start, self.end, self.new_base))
@@ -256,7 +285,9 @@ from .polish import (ConsensusSettings, PreparedBatch, plan_batches, polish_many
                      polish_zmws)  # batched ccs driver
 from . import quiver as _quiver  # noqa: E402
 from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E402,F401
-                     QuiverMultiReadMutationScorer, QvEvaluator, QvSequenceFeatures, ALL_MOVES, BASIC_MOVES)
+                     QuiverMultiReadMutationScorer, QvEvaluator, QvSequenceFeatures, ALL_MOVES, BASIC_MOVES,
+                     RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator, RefineRepeats,
+                     RefineDinucleotideRepeats)
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

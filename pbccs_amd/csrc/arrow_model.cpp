@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <set>
 #include <stdexcept>
 
 namespace pbccs {
@@ -223,6 +224,96 @@ bool apply_mutations(const std::string& tpl, std::vector<Mutation> muts, std::st
     }
     *out = s;
     return true;
+}
+
+bool apply_mutations_ex(const std::string& tpl, std::vector<MutationEx> muts, std::string* out, std::vector<int>* mtp)
+{
+    for (const MutationEx& m : muts)
+        if (!m.Valid() || m.start < 0 || m.end > (int)tpl.size()) return false;
+    std::sort(muts.begin(), muts.end());
+    // transcript (MutationsToTranscript, Mutation.cpp:130-171) -> target-to-query map (PairwiseAlignment.cpp:264-297)
+    std::string tx;
+    int tpos = 0;
+    for (const MutationEx& m : muts) {
+        for (; tpos < m.start; ++tpos) tx.push_back('M');
+        if (m.type == 0) tx.append(m.bases.size(), 'I');
+        else {
+            tx.append((size_t)(m.end - m.start), m.type == 1 ? 'D' : 'R');
+            tpos += m.end - m.start;
+        }
+    }
+    for (; tpos < (int)tpl.size(); ++tpos) tx.push_back('M');
+    mtp->clear();
+    int q = 0;
+    for (char c : tx) {
+        if (c == 'M' || c == 'R') { mtp->push_back(q); ++q; }
+        else if (c == 'D') mtp->push_back(q);
+        else ++q;
+    }
+    mtp->push_back(q);
+    // overlapping edits give a transcript longer than the template: no target-to-query map exists for them
+    if ((int)mtp->size() != (int)tpl.size() + 1) return false;
+    // real edits with a running length offset (ApplyMutations, Mutation.cpp:115-128)
+    std::string s(tpl);
+    int shift = 0;
+    for (const MutationEx& m : muts) {
+        const int at = m.start + shift;
+        const int w = m.end - m.start;
+        if (at < 0 || at + w > (int)s.size()) return false;
+        if (m.type == 2) s.replace((size_t)at, (size_t)w, m.bases);
+        else if (m.type == 1) s.erase((size_t)at, (size_t)w);
+        else s.insert((size_t)at, m.bases);
+        shift += m.LengthDiff();
+    }
+    *out = s;
+    return true;
+}
+
+void repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatElements, int begin, int end,
+                      std::vector<MutationEx>* out)
+{
+    if (minRepeatElements <= 0 || repeatLength > 31 || repeatLength < 1) return;
+    const int L = (int)tpl.size();
+    begin = std::max(0, std::min(begin, L));
+    end = std::max(0, std::min(end, L));
+    // every repeat that starts in the window; pos advances at the bottom
+    for (int pos = begin; pos + repeatLength <= end;) {
+        int numElements = 1;
+        for (int i = pos + repeatLength; i + repeatLength <= L; i += repeatLength) {
+            // beyond the window with enough elements: stop
+            if (numElements >= minRepeatElements && i >= end) break;
+            if (tpl.compare((size_t)pos, (size_t)repeatLength, tpl, (size_t)i, (size_t)repeatLength) == 0) numElements++;
+            else break;
+        }
+        if (numElements >= minRepeatElements) {
+            MutationEx ins;
+            ins.type = 0;
+            ins.start = ins.end = pos;
+            ins.bases = tpl.substr((size_t)pos, (size_t)repeatLength);
+            out->push_back(ins);
+            MutationEx del;
+            del.type = 1;
+            del.start = pos;
+            del.end = pos + repeatLength;
+            out->push_back(del);
+        }
+        // resume on the second base of the last element found, else one ahead
+        if (numElements > 1) pos += repeatLength * (numElements - 1) + 1;
+        else pos++;
+    }
+}
+
+void nearby_repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatElements,
+                             const std::vector<int>& centerStarts, int nbhd, std::vector<MutationEx>* out)
+{
+    std::set<MutationEx> all;
+    std::vector<MutationEx> part;
+    for (int c : centerStarts) {
+        part.clear();
+        repeat_mutations(tpl, repeatLength, minRepeatElements, c - nbhd, c + nbhd, &part);
+        all.insert(part.begin(), part.end());
+    }
+    out->insert(out->end(), all.begin(), all.end());
 }
 
 int probability_to_qv(double p)

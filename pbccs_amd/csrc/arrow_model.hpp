@@ -77,6 +77,47 @@ void nearby_mutations(const std::string& tpl, const std::vector<int>& centerStar
 // Returns false when an edit is out of range (the reference would throw).
 bool apply_mutations(const std::string& tpl, std::vector<Mutation> muts, std::string* out, std::vector<int>* mtp);
 
+// A mutation of any width (Mutation.hpp): type, [start, end) and the new bases.  Invariants as in
+// Mutation-inl.hpp:102-115, order as in Mutation-inl.hpp:179-186 (start, end, type, new bases).
+struct MutationEx {
+    int type = 2;    // 0 insertion, 1 deletion, 2 substitution
+    int start = 0;
+    int end = 1;
+    std::string bases;   // empty for deletions
+    bool Valid() const
+    {
+        if (type == 0) return start == end && !bases.empty();
+        if (type == 1) return start < end && bases.empty();
+        if (type == 2) return start < end && (int)bases.size() == end - start;
+        return false;
+    }
+    int LengthDiff() const { return type == 0 ? (int)bases.size() : (type == 1 ? start - end : 0); }
+    bool operator<(const MutationEx& o) const
+    {
+        if (start != o.start) return start < o.start;
+        if (end != o.end) return end < o.end;
+        if (type != o.type) return type < o.type;
+        return bases < o.bases;
+    }
+    bool operator==(const MutationEx& o) const
+    {
+        return type == o.type && start == o.start && end == o.end && bases == o.bases;
+    }
+};
+
+// ApplyMutations (Mutation.cpp:115-128), MutationsToTranscript (:130-171) and TargetToQueryPositions
+// (:193-197) for any width.  Returns false for an invalid mutation or an edit outside the template.
+bool apply_mutations_ex(const std::string& tpl, std::vector<MutationEx> muts, std::string* out, std::vector<int>* mtp);
+
+// RepeatMutationEnumerator::Mutations(begin, end) (MutationEnumerator.cpp:161-218): an insertion and a
+// deletion of one repeat element at the start of every run of >= minRepeatElements elements.
+void repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatElements, int begin, int end,
+                      std::vector<MutationEx>* out);
+// UniqueNearbyMutations (MutationEnumerator-inl.hpp:50-68) over the repeat enumerator: the union of
+// Mutations(c - nbhd, c + nbhd) over the centres, in std::set<Mutation> order.
+void nearby_repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatElements,
+                             const std::vector<int>& centerStarts, int nbhd, std::vector<MutationEx>* out);
+
 // ProbabilityToQV (Consensus-inl.hpp:130-138)
 int probability_to_qv(double p);
 

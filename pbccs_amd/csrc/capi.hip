@@ -1157,6 +1157,47 @@ int quiver_codes(const pbccs_mutation* m, int n, std::vector<int>* codes)
     return PBCCS_OK;
 }
 
+// pbccs_mutation_ex -> MutationEx; acgtOnly: the template-editing calls
+bool to_mutation_ex(const pbccs_mutation_ex& in, bool acgtOnly, bool anyBase, MutationEx* out)
+{
+    if (in.type < 0 || in.type > 2 || in.start < 0 || in.n_bases < 0) return false;
+    out->type = in.type;
+    out->start = in.start;
+    out->end = in.end;
+    out->bases.clear();
+    if (in.type != PBCCS_DELETION) {
+        if (in.n_bases > 0 && !in.new_bases) return false;
+        out->bases.assign(in.new_bases ? in.new_bases : "", (size_t)in.n_bases);
+    }
+    if (!out->Valid()) return false;
+    if (anyBase) return true;
+    if ((int)out->bases.size() > PBCCS_MAX_MUTATION_BASES) return false;
+    for (char c : out->bases) {
+        const bool acgt = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+        if (!acgt && (acgtOnly || !(c == 'M' || c == 'N'))) return false;
+    }
+    return true;
+}
+
+int quiver_mutations_ex(const pbccs_mutation_ex* m, int n, bool acgtOnly, std::vector<MutationEx>* out)
+{
+    for (int i = 0; i < n; ++i) {
+        MutationEx mu;
+        if (!to_mutation_ex(m[i], acgtOnly, false, &mu)) return fail(PBCCS_EINVAL, "invalid multi-base mutation");
+        out->push_back(mu);
+    }
+    return PBCCS_OK;
+}
+
+// the scoring calls' common front: parse, then the 8-column rule, before any launch
+int quiver_scorable_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int n, std::vector<MutationEx>* out)
+{
+    if (quiver_mutations_ex(m, n, false, out) != PBCCS_OK) return PBCCS_EINVAL;
+    if (!s->batch->ColumnsFit(s->z, *out))
+        return fail(PBCCS_EINVAL, "mutation needs more than 8 extend-buffer columns on some read");
+    return PBCCS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1289,6 +1330,137 @@ int pbccs_quiver_scorer_apply_mutations(pbccs_quiver_scorer* s, const pbccs_muta
         if (!s->batch->ApplyMutations(s->z, muts)) return fail(PBCCS_EINVAL, "mutation outside the template");
         return PBCCS_OK;
     });
+}
+
+int pbccs_quiver_scorer_score_many_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int n, int fast,
+                                      float* scores)
+{
+    if (!s || n < 0 || (n > 0 && (!m || !scores))) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        if (quiver_scorable_ex(s, m, n, &muts) != PBCCS_OK) return PBCCS_EINVAL;
+        std::vector<float> d;
+        s->batch->DeltasEx(s->z, muts, &d);
+        for (int i = 0; i < n; ++i) scores[i] = s->batch->Score(s->z, d, i, fast != 0);
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_quiver_scorer_scores_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, float unscored,
+                                  float* per_read)
+{
+    if (!s || !m || !per_read) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        if (quiver_scorable_ex(s, m, 1, &muts) != PBCCS_OK) return PBCCS_EINVAL;
+        std::vector<float> d;
+        s->batch->DeltasEx(s->z, muts, &d);
+        const int nr = s->batch->NumReads(s->z);
+        for (int k = 0; k < nr; ++k) per_read[k] = std::isnan(d[k]) ? unscored : d[k];
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_quiver_scorer_is_favorable_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int fast,
+                                        int* favorable)
+{
+    if (!s || !m || !favorable) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        if (quiver_scorable_ex(s, m, 1, &muts) != PBCCS_OK) return PBCCS_EINVAL;
+        std::vector<float> d;
+        s->batch->DeltasEx(s->z, muts, &d);
+        *favorable = fast ? (s->batch->FastIsFavorable(s->z, d, 0) ? 1 : 0)
+                          : ((double)s->batch->Score(s->z, d, 0, false) > 0.04 ? 1 : 0);
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_quiver_scorer_read_score_mutation_ex(pbccs_quiver_scorer* s, int i, const pbccs_mutation_ex* m,
+                                               float* score)
+{
+    if (!s || !m || !score || i < 0 || i >= s->batch->NumReads(s->z)) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        if (quiver_mutations_ex(m, 1, false, &muts) != PBCCS_OK) return PBCCS_EINVAL;
+        if (!s->batch->ReadScoreMutationEx(s->batch->ReadIndex(s->z, i), muts[0], score))
+            return fail(PBCCS_EINVAL, "mutation outside the read's window or needing more than 8 columns");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_quiver_scorer_apply_mutations_ex(pbccs_quiver_scorer* s, const pbccs_mutation_ex* m, int n)
+{
+    if (!s || n < 0 || (n > 0 && !m)) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        if (quiver_mutations_ex(m, n, true, &muts) != PBCCS_OK) return PBCCS_EINVAL;
+        if (!s->batch->ApplyMutationsEx(s->z, muts)) return fail(PBCCS_EINVAL, "mutation outside the template");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_quiver_refine_repeats(pbccs_quiver_scorer* s, const pbccs_repeat_options* opts, long long* n_tested,
+                                long long* n_applied, int* converged)
+{
+    if (!s || !n_tested || !n_applied || !converged) return fail(PBCCS_EINVAL, "bad argument");
+    pbccs_repeat_options o = {2, 3, 1, 10, 20};
+    if (opts) o = *opts;
+    if (o.repeat_length < 1 || o.repeat_length > PBCCS_MAX_MUTATION_BASES)
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return guarded([&] {
+        RefineOptions ro;
+        ro.maxIterations = o.max_iterations;
+        ro.mutationSeparation = o.mutation_separation;
+        ro.mutationNeighborhood = o.mutation_neighborhood;
+        bool conv = false;
+        const int rc = s->batch->RefineRepeats(s->z, o.repeat_length, o.min_repeat_elements, ro, n_tested, n_applied,
+                                               &conv);
+        if (rc == 1) return fail(PBCCS_EINVAL, "invalid edit");
+        if (rc == 2) return fail(PBCCS_EINVAL, "repeat mutation needs more than 8 extend-buffer columns on some read");
+        *converged = conv ? 1 : 0;
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_repeat_mutations(const char* tpl, int tpl_len, int repeat_length, int min_repeat_elements, int begin,
+                           int end, pbccs_mutation_ex* out, int cap, int* n)
+{
+    if (!tpl || tpl_len < 0 || !n || cap < 0 || (cap > 0 && !out) || repeat_length < 1)
+        return fail(PBCCS_EINVAL, "bad argument");
+    std::vector<MutationEx> muts;
+    repeat_mutations(std::string(tpl, (size_t)tpl_len), repeat_length, min_repeat_elements, begin, end, &muts);
+    *n = (int)muts.size();
+    if ((int)muts.size() > cap) return fail(PBCCS_ERANGE, "buffer too small");
+    for (size_t k = 0; k < muts.size(); ++k) {
+        out[k].type = muts[k].type;
+        out[k].start = muts[k].start;
+        out[k].end = muts[k].end;
+        out[k].n_bases = (int)muts[k].bases.size();
+        out[k].new_bases = muts[k].type == PBCCS_INSERTION ? tpl + muts[k].start : nullptr;
+    }
+    return PBCCS_OK;
+}
+
+int pbccs_apply_mutations(const char* tpl, int tpl_len, const pbccs_mutation_ex* muts, int n, char* out, int cap,
+                          int* len, int* mtp)
+{
+    if (!tpl || tpl_len < 0 || n < 0 || (n > 0 && !muts) || !out || !len) return fail(PBCCS_EINVAL, "bad argument");
+    std::vector<MutationEx> ms;
+    for (int i = 0; i < n; ++i) {
+        MutationEx mu;
+        if (!to_mutation_ex(muts[i], false, true, &mu)) return fail(PBCCS_EINVAL, "invalid mutation");
+        ms.push_back(mu);
+    }
+    std::string next;
+    std::vector<int> map;
+    if (!apply_mutations_ex(std::string(tpl, (size_t)tpl_len), ms, &next, &map))
+        return fail(PBCCS_EINVAL, "mutation outside the template");
+    *len = (int)next.size();
+    if ((int)next.size() + 1 > cap) return fail(PBCCS_ERANGE, "buffer too small");
+    std::memcpy(out, next.c_str(), next.size() + 1);
+    if (mtp) std::copy(map.begin(), map.end(), mtp);
+    return PBCCS_OK;
 }
 
 int pbccs_quiver_scorer_template(pbccs_quiver_scorer* s, int strand, char* out, int cap, int* len)
@@ -1455,9 +1627,11 @@ int pbccs_qv_evaluator_moves(pbccs_engine* eng, const pbccs_qv_features* read, c
     });
 }
 
-int pbccs_quiver_polish_batch(pbccs_engine* eng, const pbccs_quiver_config* configs, const char* const* chemistries,
-                              int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
-                              pbccs_quiver_result* out)
+// pbccs_quiver_polish_batch and its _ex form: rep == nullptr is the plain call
+static int quiver_polish_batch_impl(pbccs_engine* eng, const pbccs_quiver_config* configs,
+                                    const char* const* chemistries, int n_configs, const pbccs_quiver_zmw* zmws, int n,
+                                    const pbccs_refine_options* opts, const pbccs_repeat_options* rep,
+                                    long long* repeat_tested, long long* repeat_applied, pbccs_quiver_result* out)
 {
     if (!eng || !configs || n_configs < 1 || n < 0 || (n > 0 && (!zmws || !out))) return fail(PBCCS_EINVAL, "bad argument");
     for (int k = 0; k < n_configs; ++k)
@@ -1551,6 +1725,27 @@ int pbccs_quiver_polish_batch(pbccs_engine* eng, const pbccs_quiver_config* conf
         std::vector<long long> nt, na;
         std::vector<char> conv, ok;
         qb.RefineMany(zs, ro, &nt, &na, &conv, &ok);
+        if (rep) {   // RefineRepeats on the scorers RefineConsensus left usable, in lock-step rounds
+            std::vector<int> rk, rz;
+            for (int z = 0; z < n; ++z) {
+                if (repeat_tested) repeat_tested[z] = 0;
+                if (repeat_applied) repeat_applied[z] = 0;
+                if (ok[z]) { rk.push_back(z); rz.push_back(zs[z]); }
+            }
+            RefineOptions rr;
+            rr.maxIterations = rep->max_iterations;
+            rr.mutationSeparation = rep->mutation_separation;
+            rr.mutationNeighborhood = rep->mutation_neighborhood;
+            std::vector<long long> rt, ra;
+            std::vector<char> rconv;
+            std::vector<int> rst;
+            qb.RefineRepeatsMany(rz, rep->repeat_length, rep->min_repeat_elements, rr, &rt, &ra, &rconv, &rst);
+            for (size_t k = 0; k < rk.size(); ++k) {
+                if (repeat_tested) repeat_tested[rk[k]] = rt[k];
+                if (repeat_applied) repeat_applied[rk[k]] = ra[k];
+                if (rst[k] != 0) ok[rk[k]] = 0;
+            }
+        }
         const double msRefine = lap();
         std::vector<int> wantQv;
         for (int z = 0; z < n; ++z)
@@ -1581,6 +1776,24 @@ int pbccs_quiver_polish_batch(pbccs_engine* eng, const pbccs_quiver_config* conf
         }
         return PBCCS_OK;
     });
+}
+
+int pbccs_quiver_polish_batch(pbccs_engine* eng, const pbccs_quiver_config* configs, const char* const* chemistries,
+                              int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
+                              pbccs_quiver_result* out)
+{
+    return quiver_polish_batch_impl(eng, configs, chemistries, n_configs, zmws, n, opts, nullptr, nullptr, nullptr, out);
+}
+
+int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* configs, const char* const* chemistries,
+                                 int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
+                                 const pbccs_repeat_options* repeats, long long* repeat_tested,
+                                 long long* repeat_applied, pbccs_quiver_result* out)
+{
+    if (repeats && (repeats->repeat_length < 1 || repeats->repeat_length > PBCCS_MAX_MUTATION_BASES))
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return quiver_polish_batch_impl(eng, configs, chemistries, n_configs, zmws, n, opts, repeats, repeat_tested,
+                                    repeat_applied, out);
 }
 
 // ---------------------------------------------------------------- POA draft

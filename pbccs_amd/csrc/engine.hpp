@@ -258,10 +258,10 @@ void ckpt_policy(int* K, int* minLen);
 // tall bands (launched on their own streams), reported apart so each kind's launches never overlap each other
 // within one workspace slot
 // The Quiver family's kinds (kKQ*) are the QuiverBatch fills (four reads per wavefront, a wave per read on the side
-// stream, the lane-serial fill) and its batched middle-case scoring.
+// stream, the lane-serial fill) its batched middle-case scoring and the repeat rounds' multi-base scoring (cells = tasks).
 enum KernelKind {
     kKFill = 0, kKSuffix, kKEnumerate, kKScore, kKReduce, kKQv, kKSelect, kKCompact, kKFillTall,
-    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKernelKinds
+    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKernelKinds
 };
 extern const char* const kKernelNames[kKernelKinds];
 

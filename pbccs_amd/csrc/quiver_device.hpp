@@ -142,6 +142,7 @@ struct QTpl {
     int editPos = -1;    // position of the edit in the unedited template (-1: none)
     int editType = 0;    // 0 insertion, 1 deletion, 2 substitution (single base)
     int editBase = 0;    // a char (int: byte-sized members of a by-value struct were kept in scratch)
+    static constexpr bool kWide = false;
     __device__ __forceinline__ char at(int j) const   // std::string semantics: '\0' at j == len
     {
         if (j >= len) return '\0';
@@ -152,12 +153,35 @@ struct QTpl {
     }
 };
 
+// The same with an edit of any width (k_qscore_multi): nDel bases of the unedited template at editPos are
+// replaced by nIns new bases, base k of them in byte k of `bases` (at most 7: the extend buffer has 8 columns).
+struct QTplWide {
+    const char* base;
+    int len;             // length of the edited template
+    int editPos = -1;
+    int nIns = 0;
+    int nDel = 0;
+    unsigned long long bases = 0;
+    static constexpr bool kWide = true;
+    __device__ __forceinline__ char at(int j) const
+    {
+        if (j >= len) return '\0';
+        if (editPos < 0 || j < editPos) return base[j];
+        if (j < editPos + nIns) return (char)((bases >> (8 * (j - editPos))) & 0xffull);
+        return base[j - nIns + nDel];
+    }
+};
+
 __device__ __forceinline__ int tpl_code(char b) { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : 3; }
 
-struct QEval {
+template <class V>
+struct QEvalT {
     QRead r;   // by value: a pointer to a kernel-local QRead would keep it in scratch
     const QParams* p;
-    QTpl t;
+    V t;
+    // a wide edit moves the recursions' merge reads past the band's first / last column, where the reference
+    // reads outside its matrix: those cells count as unset (band_get)
+    static constexpr bool kWide = V::kWide;
     __device__ __forceinline__ int I() const { return r.I; }
     __device__ __forceinline__ int J() const { return t.len; }
     __device__ __forceinline__ float Inc(int i, int j) const
@@ -181,6 +205,8 @@ struct QEval {
         return p->Merge[k] + p->MergeS[k] * r.merge[i];
     }
 };
+struct QEval : QEvalT<QTpl> {};   // a type of its own: k_qv_moves takes it by value and keeps its symbol
+using QEvalWide = QEvalT<QTplWide>;
 
 // ---- band matrix --------------------------------------------------------------------------------------
 // One pass of one matrix lives in one arena: per column range[j] = used rows, off[j] = arena offset of
@@ -200,6 +226,13 @@ struct QBand {
     }
     __device__ __forceinline__ bool Empty(int j) const { const int2 r = range[j]; return r.x >= r.y; }
 };
+// Get with a column check for the wide view's recursions; the single-base ones never leave the band
+template <bool WIDE>
+__device__ __forceinline__ float band_get(const QBand& m, int i, int j)
+{
+    if (WIDE && (j < 0 || j >= m.cols)) return kNegInf;
+    return m.Get(i, j);
+}
 
 // SparseVector<float> allocation bookkeeping (SparseVector-inl.hpp:48-141, 171-186, 250-255) for
 // AllocatedEntries = storage_.capacity(), as libstdc++'s vector grows it: resize(n) above the capacity

@@ -650,12 +650,13 @@ void QuiverBatch::Deltas(int zi, const std::vector<int>& codes, std::vector<floa
 }
 
 void QuiverBatch::RunScore(const std::vector<int>& tr, const std::vector<int>& tm, const std::vector<int>& codes,
-                           bool raw, std::vector<float>* out)
+                           bool raw, std::vector<float>* out, const std::vector<QMutRec>* muts)
 {
     Upload();
     put(dTaskRead_, tr, stream_);
     put(dTaskMut_, tm, stream_);
-    put(dCodes_, codes, stream_);
+    if (muts) put(dMuts_, *muts, stream_);   // k_qscore_multi: taskMut indexes the records
+    else put(dCodes_, codes, stream_);
     dDelta_.reserve(std::max<size_t>(tr.size(), 1), false);
     for (int attempt = 0;; ++attempt) {
         QHIP(hipMemsetAsync(dScratchTop_.ptr, 0, sizeof(unsigned long long), stream_));
@@ -671,7 +672,14 @@ void QuiverBatch::RunScore(const std::vector<int>& tr, const std::vector<int>& t
         W.overflow = dOverflow_.ptr;
         W.nTasks = (long long)tr.size();
         W.raw = raw ? 1 : 0;
-        launch_qscore(View(), W, stream_);
+        if (muts) {
+            QMultiWork M;
+            M.w = W;
+            M.muts = dMuts_.ptr;
+            launch_qscore_multi(View(), M, stream_);
+        } else {
+            launch_qscore(View(), W, stream_);
+        }
         QHIP(hipGetLastError());
         int ovf = 0;
         unsigned long long top = 0;
@@ -795,6 +803,167 @@ bool QuiverBatch::Refine(int zi, const RefineOptions& ro, long long* nTested, lo
         if (!ApplyMutations(zi, muts)) return false;
     }
     return true;
+}
+
+// ---- mutations of any width ----------------------------------------------------------------------------
+namespace {
+
+bool base_ok(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'M' || c == 'N'; }
+
+bool record_of(const MutationEx& m, QMutRec* rec)
+{
+    if (!m.Valid() || m.start < 0 || (int)m.bases.size() > kQMaxBases) return false;
+    rec->type = m.type;
+    rec->start = m.start;
+    rec->end = m.end;
+    rec->nBases = (int)m.bases.size();
+    rec->bases = 0;
+    for (size_t k = 0; k < m.bases.size(); ++k) {
+        if (!base_ok(m.bases[k])) return false;
+        rec->bases |= (unsigned long long)(unsigned char)m.bases[k] << (8 * k);
+    }
+    return true;
+}
+
+// extend-buffer columns ScoreMutation needs (Quiver/MutationScorer.cpp:145-240) for a mutation [os, oe) with
+// nb new bases in a window of J columns
+int columns_needed(int type, int os, int oe, int nb, int J)
+{
+    const int lengthDiff = type == 0 ? nb : (type == 1 ? os - oe : 0);
+    const int newLen = J + lengthDiff;
+    const bool atBegin = os < 3, atEnd = oe > J - 2;
+    if (!atBegin && !atEnd) return type == 1 ? 2 : 1 + nb;
+    if (!atBegin) return newLen - (os - 1) + 1;
+    if (!atEnd) return oe + lengthDiff + 1;
+    return newLen + 1;
+}
+
+struct ScoredEx {
+    int idx, pos;
+    float score;
+};
+
+std::vector<ScoredEx> best_subset_ex(std::vector<ScoredEx> in, int sep)   // Consensus-inl.hpp:98-118
+{
+    if (sep == 0) return in;
+    std::vector<ScoredEx> out;
+    while (!in.empty()) {
+        size_t best = 0;
+        for (size_t k = 1; k < in.size(); ++k)
+            if (in[best].score < in[k].score) best = k;
+        const ScoredEx b = in[best];
+        out.push_back(b);
+        std::vector<ScoredEx> keep;
+        for (const ScoredEx& s : in)
+            if (!(b.pos - sep <= s.pos && s.pos <= b.pos + sep)) keep.push_back(s);
+        in.swap(keep);
+    }
+    return out;
+}
+
+}  // namespace
+
+bool QuiverBatch::ColumnsFit(int zi, const std::vector<MutationEx>& muts) const
+{
+    const HZmw& z = zmws_.at(zi);
+    for (const MutationEx& m : muts) {
+        QMutRec rec;
+        if (!record_of(m, &rec)) return false;
+        for (int r : z.reads) {
+            const HRead& h = reads_[r];
+            if (!h.active) continue;
+            const bool scores = m.type == 0 ? (h.ts < m.start && m.end <= h.te) : (h.ts < m.end && m.start < h.te);
+            if (!scores) continue;
+            // OrientedMutation (Quiver/MultiReadMutationScorer.cpp:80-124): the clip, then the strand
+            int ms = m.start, me = m.end, nb = rec.nBases;
+            if (me - ms > 1) {
+                ms = std::max(ms, h.ts);
+                me = std::min(me, h.te);
+                if (m.type == 2) nb = me - ms;
+            }
+            const int os = h.strand == 0 ? ms - h.ts : h.te - me;
+            const int oe = h.strand == 0 ? me - h.ts : h.te - ms;
+            if (columns_needed(m.type, os, oe, nb, h.te - h.ts) > kQExtendColumns) return false;
+        }
+    }
+    return true;
+}
+
+void QuiverBatch::DeltasEx(int zi, const std::vector<MutationEx>& muts, std::vector<float>* out)
+{
+    const HZmw& z = zmws_.at(zi);
+    const int nr = (int)z.reads.size();
+    out->assign(muts.size() * (size_t)nr, std::numeric_limits<float>::quiet_NaN());
+    std::vector<QMutRec> recs(muts.size());
+    std::vector<int> tr, tm;
+    std::vector<size_t> slot;
+    for (size_t m = 0; m < muts.size(); ++m) {
+        if (!record_of(muts[m], &recs[m])) throw DeviceError("invalid multi-base mutation");
+        for (int k = 0; k < nr; ++k) {
+            if (!reads_[z.reads[k]].active) continue;   // inactive reads: NaN, as Deltas
+            tr.push_back(z.reads[k]);
+            tm.push_back((int)m);
+            slot.push_back(m * (size_t)nr + k);
+        }
+    }
+    if (tr.empty()) return;
+    std::vector<float> d;
+    RunScore(tr, tm, {}, false, &d, &recs);
+    for (size_t t = 0; t < slot.size(); ++t) (*out)[slot[t]] = d[t];
+}
+
+bool QuiverBatch::ReadScoreMutationEx(int r, const MutationEx& m, float* score)
+{
+    const HRead& h = reads_.at(r);
+    QMutRec rec;
+    if (!record_of(m, &rec)) return false;
+    const int J = h.te - h.ts;
+    if (m.end > J) return false;
+    if (columns_needed(m.type, m.start, m.end, rec.nBases, J) > kQExtendColumns) return false;
+    if (!h.hasScorer) {
+        *score = 0.0f;
+        return true;
+    }
+    std::vector<float> d;
+    std::vector<QMutRec> recs(1, rec);
+    RunScore({r}, {0}, {}, true, &d, &recs);
+    *score = d[0];
+    return true;
+}
+
+bool QuiverBatch::ApplyMutationsEx(int zi, const std::vector<MutationEx>& muts)   // :205-239
+{
+    HZmw& z = zmws_.at(zi);
+    std::string next;
+    std::vector<int> mtp;
+    if (!apply_mutations_ex(z.tpl, muts, &next, &mtp) || next.empty()) return false;
+    z.tpl = next;
+    std::vector<int> refill;
+    for (int r : z.reads) {
+        HRead& h = reads_[r];
+        h.ts = mtp[h.ts];
+        h.te = mtp[h.te];
+        if (h.active) {
+            EnsureCapacity(r);
+            refill.push_back(r);
+        }
+    }
+    dirty_ = true;
+    Fill(refill);   // a refill that mismatches marks the read inactive
+    return true;
+}
+
+int QuiverBatch::RefineRepeats(int zi, int repeatLength, int minRepeatElements, const RefineOptions& ro,
+                               long long* nTested, long long* nApplied, bool* converged)
+{
+    std::vector<long long> nt, na;
+    std::vector<char> conv;
+    std::vector<int> st;
+    RefineRepeatsMany({zi}, repeatLength, minRepeatElements, ro, &nt, &na, &conv, &st);
+    *nTested = nt[0];
+    *nApplied = na[0];
+    *converged = conv[0] != 0;
+    return st[0];
 }
 
 bool QuiverBatch::Alignment(int r, std::string* target, std::string* query)
@@ -1153,6 +1322,199 @@ void QuiverBatch::RefineMany(const std::vector<int>& zs, const RefineOptions& ro
         if (trace)
             std::fprintf(stderr, "[quiver] round %d scorers %zu enumerate %.1f ms score %.1f ms apply %.1f ms fill %.1f ms\n",
                          round, act.size(), msEnum, msScore, msApply, msSince(tr3));
+    }
+}
+
+// ---- repeat rounds -------------------------------------------------------------------------------------------
+void QuiverBatch::ScoreRoundEx(const std::vector<int>& zs, const std::vector<std::vector<MutationEx>>& cand,
+                               std::vector<long long>* mutStartOut, std::vector<double>* score,
+                               std::vector<unsigned char>* fav)
+{
+    const int n = (int)zs.size();
+    std::vector<long long> taskStart(n + 1, 0);
+    std::vector<long long>& mutStart = *mutStartOut;
+    mutStart.assign(n + 1, 0);
+    std::vector<int> readBase(n), nReads(n), readList;
+    std::vector<float> fastThr(n);
+    std::vector<QMutRec> recs;
+    for (int w = 0; w < n; ++w) {
+        const HZmw& z = zmws_[zs[w]];
+        readBase[w] = (int)readList.size();
+        nReads[w] = (int)z.reads.size();
+        readList.insert(readList.end(), z.reads.begin(), z.reads.end());
+        fastThr[w] = z.fastThreshold;
+        for (const MutationEx& m : cand[w]) {
+            QMutRec rec;
+            if (!record_of(m, &rec)) throw DeviceError("invalid multi-base mutation");
+            recs.push_back(rec);
+        }
+        mutStart[w + 1] = mutStart[w] + (long long)cand[w].size();
+        taskStart[w + 1] = taskStart[w] + (long long)cand[w].size() * nReads[w];
+    }
+    const long long nTask = taskStart[n], nMut = mutStart[n];
+    score->assign((size_t)nMut, 0.0);
+    fav->assign((size_t)nMut, 0);
+    if (nMut == 0) return;
+    std::vector<int> active(reads_.size());
+    for (size_t r = 0; r < reads_.size(); ++r) active[r] = reads_[r].active ? 1 : 0;
+    Upload();
+    put(dWTaskStart_, taskStart, stream_);
+    put(dWMutBase_, mutStart, stream_);
+    put(dWReadBase_, readBase, stream_);
+    put(dWNReads_, nReads, stream_);
+    put(dReadList_, readList, stream_);
+    put(dRActive_, active, stream_);
+    put(dWFast_, fastThr, stream_);
+    put(dMuts_, recs, stream_);
+    dDelta_.reserve(std::max<long long>(nTask, 1), false);
+    for (long long t0 = 0; t0 < nTask;) {
+        const long long m = std::min(kTaskChunk, nTask - t0);
+        for (int attempt = 0;; ++attempt) {
+            QHIP(hipMemsetAsync(dScratchTop_.ptr, 0, sizeof(unsigned long long), stream_));
+            QHIP(hipMemsetAsync(dOverflow_.ptr, 0, sizeof(int), stream_));
+            QMultiWork M;
+            QScoreWork& W = M.w;
+            W.taskRead = nullptr;
+            W.taskMut = nullptr;
+            W.codes = nullptr;
+            W.delta = dDelta_.ptr;
+            W.scratch = dScratch_.ptr;
+            W.scratchTop = dScratchTop_.ptr;
+            W.scratchCap = dScratch_.cap;
+            W.overflow = dOverflow_.ptr;
+            W.nTasks = m;
+            W.raw = 0;
+            W.nWork = n;
+            W.taskBase = t0;
+            W.wTaskStart = dWTaskStart_.ptr;
+            W.wMutBase = dWMutBase_.ptr;
+            W.wReadBase = dWReadBase_.ptr;
+            W.wNReads = dWNReads_.ptr;
+            W.readList = dReadList_.ptr;
+            W.rActive = dRActive_.ptr;
+            M.muts = dMuts_.ptr;
+            Timed(kKQScoreMulti, [&] { launch_qscore_multi(View(), M, stream_); }, stream_);
+            QHIP(hipGetLastError());
+            int ovf = 0;
+            unsigned long long top = 0;
+            QHIP(hipMemcpyAsync(&ovf, dOverflow_.ptr, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            QHIP(hipMemcpyAsync(&top, dScratchTop_.ptr, sizeof(top), hipMemcpyDeviceToHost, stream_));
+            QHIP(hipStreamSynchronize(stream_));
+            if (!ovf) break;
+            if ((ovf & 2) || attempt > 6) throw DeviceError("quiver extend buffer exceeds 8 columns / scratch");
+            grow_scratch(top);
+        }
+        if (profiling_) stats_[kKQScoreMulti].cells += (double)m;
+        t0 += m;
+    }
+    dMScore_.reserve(std::max<long long>(nMut, 1), false);
+    dFav_.reserve(std::max<long long>(nMut, 1), false);
+    QReduceWork R;
+    R.nWork = n;
+    R.wMutStart = dWMutBase_.ptr;
+    R.wTaskStart = dWTaskStart_.ptr;
+    R.wNReads = dWNReads_.ptr;
+    R.wFastThreshold = dWFast_.ptr;
+    R.delta = dDelta_.ptr;
+    R.score = dMScore_.ptr;
+    R.fav = dFav_.ptr;
+    R.nMut = nMut;
+    launch_qreduce(R, stream_);
+    QHIP(hipGetLastError());
+    get(*score, dMScore_, (size_t)nMut, stream_);
+    get(*fav, dFav_, (size_t)nMut, stream_);
+    QHIP(hipStreamSynchronize(stream_));
+}
+
+// AbstractRefineConsensus (Consensus-inl.hpp:159-251) over RepeatMutationEnumerator, scorers in lock-step
+void QuiverBatch::RefineRepeatsMany(const std::vector<int>& zs, int repeatLength, int minRepeatElements,
+                                    const RefineOptions& ro, std::vector<long long>* nTested,
+                                    std::vector<long long>* nApplied, std::vector<char>* converged,
+                                    std::vector<int>* status)
+{
+    const int n = (int)zs.size();
+    nTested->assign(n, 0);
+    nApplied->assign(n, 0);
+    converged->assign(n, 0);
+    status->assign(n, 0);
+    std::vector<char> done(n, 0);
+    std::vector<int> iter(n, 0);
+    std::vector<std::set<std::string>> history(n);
+    std::vector<std::vector<int>> centers(n);
+    if (ro.maxIterations <= 0) return;
+    for (;;) {
+        std::vector<int> act, idx;
+        std::vector<std::vector<MutationEx>> cand;
+        for (int k = 0; k < n; ++k) {
+            if (done[k]) continue;
+            const std::string& tpl = zmws_[zs[k]].tpl;
+            std::vector<MutationEx> c;
+            if (iter[k] == 0) repeat_mutations(tpl, repeatLength, minRepeatElements, 0, (int)tpl.size(), &c);
+            else nearby_repeat_mutations(tpl, repeatLength, minRepeatElements, centers[k], ro.mutationNeighborhood, &c);
+            if (!ColumnsFit(zs[k], c)) {   // the 8-column rule: nothing of this scorer is scored
+                (*status)[k] = 2;
+                done[k] = 1;
+                continue;
+            }
+            (*nTested)[k] += (long long)c.size();
+            act.push_back(zs[k]);
+            idx.push_back(k);
+            cand.push_back(std::move(c));
+        }
+        if (act.empty()) break;
+        std::vector<long long> mutStart;
+        std::vector<double> score;
+        std::vector<unsigned char> favFlag;
+        ScoreRoundEx(act, cand, &mutStart, &score, &favFlag);
+        std::vector<int> refill;
+        for (size_t a = 0; a < act.size(); ++a) {
+            const int k = idx[a];
+            HZmw& z = zmws_[act[a]];
+            std::vector<ScoredEx> fav;
+            for (int m = 0; m < (int)cand[a].size(); ++m)
+                if (favFlag[(size_t)(mutStart[a] + m)])
+                    fav.push_back({m, cand[a][m].start, (float)score[(size_t)(mutStart[a] + m)]});
+            if (fav.empty()) {
+                (*converged)[k] = 1;
+                done[k] = 1;
+                continue;
+            }
+            std::vector<ScoredEx> best = best_subset_ex(fav, ro.mutationSeparation);
+            std::vector<MutationEx> muts;
+            for (const ScoredEx& s : best) muts.push_back(cand[a][s.idx]);
+            if (best.size() > 1) {
+                std::string nx;
+                std::vector<int> mtp;
+                if (apply_mutations_ex(z.tpl, muts, &nx, &mtp) && history[k].count(nx)) {
+                    best.resize(1);
+                    muts.resize(1);
+                }
+            }
+            (*nApplied)[k] += (long long)best.size();
+            history[k].insert(z.tpl);
+            centers[k].clear();
+            for (const ScoredEx& s : fav) centers[k].push_back(s.pos);
+            std::string next;
+            std::vector<int> mtp;
+            if (!apply_mutations_ex(z.tpl, muts, &next, &mtp) || next.empty()) {
+                (*status)[k] = 1;
+                done[k] = 1;
+                continue;
+            }
+            z.tpl = next;
+            for (int r : z.reads) {
+                HRead& h = reads_[r];
+                h.ts = mtp[h.ts];
+                h.te = mtp[h.te];
+                if (h.active) {
+                    EnsureCapacity(r);
+                    refill.push_back(r);
+                }
+            }
+            dirty_ = true;
+            if (++iter[k] >= ro.maxIterations) done[k] = 1;
+        }
+        if (!refill.empty()) Fill(refill);   // a refill that mismatches marks the read inactive
     }
 }
 

@@ -106,6 +106,27 @@ public:
     bool Refine(int z, const RefineOptions& ro, long long* nTested, long long* nApplied, bool* converged);
     std::vector<int> QVs(int z);
 
+    // ---- mutations of any width (k_qscore_multi) -------------------------------------------------------
+    // The 8-column rule: false when some (active read, mutation) pair that the read scores would need more
+    // than the extend buffer's 8 columns (ScoreMutation's begin / end / whole-fill cases, or 1 + n bases in
+    // the middle), or when a mutation is invalid or holds more than kQMaxBases bases.  Nothing is launched.
+    bool ColumnsFit(int z, const std::vector<MutationEx>& muts) const;
+    // Deltas for mutations of any width (the caller has checked ColumnsFit); out[m * nReads + k]
+    void DeltasEx(int z, const std::vector<MutationEx>& muts, std::vector<float>* out);
+    // ReadScoreMutation for any width; false when the mutation leaves the read's window or the 8 columns
+    bool ReadScoreMutationEx(int r, const MutationEx& m, float* score);
+    bool ApplyMutationsEx(int z, const std::vector<MutationEx>& muts);
+    // AbstractRefineConsensus (Consensus-inl.hpp:159-251) over RepeatMutationEnumerator.  Returns 0, or 1 when
+    // ApplyMutations refused an edit, or 2 when a candidate breaks the 8-column rule (nothing more is scored).
+    int RefineRepeats(int z, int repeatLength, int minRepeatElements, const RefineOptions& ro, long long* nTested,
+                      long long* nApplied, bool* converged);
+    // The same on every listed scorer in lock-step rounds: one k_qscore_multi launch series over all scorers'
+    // candidates, one k_qreduce and one refill per round; BestSubset on the host (a scorer has few repeat
+    // candidates).  status[k]: RefineRepeats' return value.
+    void RefineRepeatsMany(const std::vector<int>& zs, int repeatLength, int minRepeatElements, const RefineOptions& ro,
+                           std::vector<long long>* nTested, std::vector<long long>* nApplied,
+                           std::vector<char>* converged, std::vector<int>* status);
+
     // ---- batched forms (pbccs_quiver_polish_batch): many scorers in lock-step rounds ------------------
     // a read of the batch path: the caller's buffers (bases and five tracks of len entries; a null track reads
     // as zeros), copied once into the engine's host pools
@@ -169,7 +190,7 @@ private:
     QBatch View();
     void Fill(const std::vector<int>& reads);
     void RunScore(const std::vector<int>& taskRead, const std::vector<int>& taskMut, const std::vector<int>& codes,
-                  bool raw, std::vector<float>* d);
+                  bool raw, std::vector<float>* d, const std::vector<QMutRec>* muts = nullptr);
     // One batched scoring round over scorers zs with their mutation lists: per scorer the favourable
     // mutations (list order, float scores) and, with sep >= 0, BestSubset's picks (pick order) from the
     // device select.
@@ -179,6 +200,9 @@ private:
     };
     void ScoreDeltas(const std::vector<int>& zs, const std::vector<std::vector<int>>& codes,
                      std::vector<long long>* taskStart, std::vector<long long>* mutStart);
+    // ScoreDeltas for candidates of any width, then k_qreduce: per candidate the float Score and FastIsFavorable
+    void ScoreRoundEx(const std::vector<int>& zs, const std::vector<std::vector<MutationEx>>& cand,
+                      std::vector<long long>* mutStart, std::vector<double>* score, std::vector<unsigned char>* fav);
     void ScoreRound(const std::vector<int>& zs, const std::vector<std::vector<int>>& codes, int sep,
                     std::vector<std::vector<Scored>>* fav, std::vector<std::vector<Scored>>* picked);
     // after a scoring launch whose extension scratch overflowed: grow it to the floats the launch asked for
@@ -219,6 +243,7 @@ private:
     DevVec<char> dTpl_, dSeq_;
     DevVec<float> dFeat_, dRScore_, dDelta_, dScratch_;
     DevVec<QParams> dParams_;
+    DevVec<QMutRec> dMuts_;
     DevVec<int2> dRange_;
     DevVec<QAlloc> dAlloc_;
     DevVec<int4> dHint_;

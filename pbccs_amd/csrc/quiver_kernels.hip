@@ -5,6 +5,8 @@
 //   k_qscore   one lane per (mutation, read): MutationScorer::ScoreMutation (Quiver/MutationScorer.cpp:
 //              113-226) -- ExtendAlpha + LinkAlphaBeta in the middle, ExtendAlpha to the end, ExtendBeta
 //              (SimpleRecursor.cpp:407-495) at the start, a whole FillAlpha for tiny windows.
+//   k_qscore_multi   the same for mutations of any width (QMutRec, the QTplWide view): OrientedMutation's clip
+//              and reverse complement, ScoreMutation's four cases with general lengths.
 // The 4-row SSE blocks are evaluated row by row in the reference's order: the block terms (Inc, Merge,
 // Del, each combined from -FLT_MAX), then the serial Extra cascade, then the block's min / max for the
 // band test -- every value equals the SSE lane's.
@@ -63,7 +65,8 @@ __device__ __forceinline__ void put(const QBand& m, long long k, float v, bool& 
 
 // Where column j's first used row goes in its arena: packed after the previous columns (SparseMatrixF), or
 // at j * (I + 1) + row (DenseMatrixF: every cell has its place, DenseMatrix-inl.hpp:212-221).
-__device__ __forceinline__ long long col_base(const QEval& e, int j, int beginRow, long long used)
+template <class E>
+__device__ __forceinline__ long long col_base(const E& e, int j, int beginRow, long long used)
 {
     return e.p->dense ? (long long)j * (e.I() + 1) + beginRow : used;
 }
@@ -76,7 +79,8 @@ __device__ __forceinline__ long long values_needed(const QEval& e, long long use
 // ---- SseRecursor::FillAlpha (SseRecursor.cpp:73-213) -----------------------------------------------------
 // `prev`: this matrix's previous pass (RangeGuide's self hint); `out`: the arena written now.  Rows come
 // top-down, so column j's cells are appended at `used` as they are produced.
-__device__ __forceinline__ long long fill_alpha(const QEval& e, const QBand* guide, const QBand* prev, const QBand& out,
+template <class E>
+__device__ __forceinline__ long long fill_alpha(const E& e, const QBand* guide, const QBand* prev, const QBand& out,
                                 QAlloc* alloc, bool allocExists, bool& ovf)
 {
     const int I = e.I(), J = e.J();
@@ -247,7 +251,8 @@ __device__ __forceinline__ long long fill_beta(const QEval& e, const QBand* guid
 }
 
 // ---- SseRecursor::ExtendAlpha (SseRecursor.cpp:433-551) --------------------------------------------------
-__device__ __forceinline__ void extend_alpha(const QEval& e, const QBand& a, int beginColumn, const QBand& ext, int numExt, bool& ovf)
+template <class E>
+__device__ __forceinline__ void extend_alpha(const E& e, const QBand& a, int beginColumn, const QBand& ext, int numExt, bool& ovf)
 {
     const bool sp = e.p->sumProduct != 0;
     const bool merge = (e.p->moves & kMerge) != 0;
@@ -270,7 +275,7 @@ __device__ __forceinline__ void extend_alpha(const QEval& e, const QBand& a, int
             if (i > 0) {
                 score = comb(sp, score, prevCol(i - 1) + e.Inc(i - 1, j - 1));
                 score = comb(sp, score, ext.Get(i - 1, c) + e.Extra(i - 1, j));
-                if (merge) score = comb(sp, score, a.Get(i - 1, j - 2) + e.Merge(i - 1, j - 2));
+                if (merge) score = comb(sp, score, band_get<E::kWide>(a, i - 1, j - 2) + e.Merge(i - 1, j - 2));
             }
             score = comb(sp, score, prevCol(i) + e.Del(i, j - 1));
             set(i, score);
@@ -282,7 +287,7 @@ __device__ __forceinline__ void extend_alpha(const QEval& e, const QBand& a, int
                 const int r = i + k;
                 float v = kNegInf;
                 v = comb4(sp, v, prevCol(r - 1) + e.Inc(r - 1, j - 1));
-                if (merge && j >= 2) v = comb4(sp, v, a.Get(r - 1, j - 2) + e.Merge(r - 1, j - 2));
+                if (merge && j >= 2) v = comb4(sp, v, band_get<E::kWide>(a, r - 1, j - 2) + e.Merge(r - 1, j - 2));
                 v = comb4(sp, v, prevCol(r) + e.Del(r, j - 1));
                 s5[k + 1] = v;
             }
@@ -298,7 +303,8 @@ __device__ __forceinline__ void extend_alpha(const QEval& e, const QBand& a, int
 
 // ---- SimpleRecursor::ExtendAlpha (Quiver/SimpleRecursor.cpp:303-388) --------------------------------------
 // Row by row; the merge term reads alpha(i - 1, j - 2) for every extension column, as the reference does.
-__device__ __forceinline__ void extend_alpha_simple(const QEval& e, const QBand& a, int beginColumn, const QBand& ext,
+template <class E>
+__device__ __forceinline__ void extend_alpha_simple(const E& e, const QBand& a, int beginColumn, const QBand& ext,
                                                     int numExt, bool& ovf)
 {
     const bool sp = e.p->sumProduct != 0;
@@ -322,7 +328,7 @@ __device__ __forceinline__ void extend_alpha_simple(const QEval& e, const QBand&
                 const float prev = c == 0 ? a.Get(i, j - 1) : ext.Get(i, c - 1);
                 score = comb(sp, score, prev + e.Del(i, j - 1));
             }
-            if (merge && j > 1 && i > 0) score = comb(sp, score, a.Get(i - 1, j - 2) + e.Merge(i - 1, j - 2));
+            if (merge && j > 1 && i > 0) score = comb(sp, score, band_get<E::kWide>(a, i - 1, j - 2) + e.Merge(i - 1, j - 2));
             put(ext, used + (i - beginRow), score, ovf);
             ext.range[c].y = i + 1;
         }
@@ -332,7 +338,8 @@ __device__ __forceinline__ void extend_alpha_simple(const QEval& e, const QBand&
 }
 
 // ---- SimpleRecursor::ExtendBeta (Quiver/SimpleRecursor.cpp:407-495) ---------------------------------------
-__device__ __forceinline__ void extend_beta(const QEval& e, const QBand& b, int lastColumn, const QBand& ext, int numExt,
+template <class E>
+__device__ __forceinline__ void extend_beta(const E& e, const QBand& b, int lastColumn, const QBand& ext, int numExt,
                             int lengthDiff, bool& ovf)
 {
     const bool sp = e.p->sumProduct != 0;
@@ -362,7 +369,7 @@ __device__ __forceinline__ void extend_beta(const QEval& e, const QBand& b, int 
                 const float prev = (c == lastExt) ? b.Get(i, j + 1) : ext.Get(i, c + 1);
                 score = comb(sp, score, prev + e.Del(i, jp));
             }
-            if (merge && j < J - 1 && i < I) score = comb(sp, score, b.Get(i + 1, j + 2) + e.Merge(i, jp));
+            if (merge && j < J - 1 && i < I) score = comb(sp, score, band_get<E::kWide>(b, i + 1, j + 2) + e.Merge(i, jp));
             put(ext, used + (i - beginRow), score, ovf);
         }
         used += max(0, endRow - beginRow);
@@ -370,7 +377,8 @@ __device__ __forceinline__ void extend_beta(const QEval& e, const QBand& b, int 
 }
 
 // ---- SseRecursor::LinkAlphaBeta (SseRecursor.cpp:355-431) ------------------------------------------------
-__device__ __forceinline__ float link_alpha_beta(const QEval& e, const QBand& a, int ac, const QBand& b, int bc, int absc)
+template <class E>
+__device__ __forceinline__ float link_alpha_beta(const E& e, const QBand& a, int ac, const QBand& b, int bc, int absc)
 {
     const bool sp = e.p->sumProduct != 0;
     const bool merge = (e.p->moves & kMerge) != 0;
@@ -1834,6 +1842,159 @@ __global__ void __launch_bounds__(64) k_qscore(QBatch B, QScoreWork W)
     W.delta[t] = W.raw ? score : score - B.rScore[r];
 }
 
+// ---- k_qscore_multi: the same for mutations of any width (QMutRec) ---------------------------------------
+// ReadScoresMutation in template coordinates, OrientedMutation with its clip of a wide mutation to the read's
+// window (Quiver/MultiReadMutationScorer.cpp:60-124), then ScoreMutation's four cases with general lengths
+// (Quiver/MutationScorer.cpp:145-240) over the wide template view.
+__device__ __forceinline__ unsigned long long comp_base(unsigned long long c)   // Sequence.cpp:41-78, M <-> N included
+{
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'M' ? 'N' : c == 'N' ? 'M' : c;
+}
+
+__global__ void __launch_bounds__(64) k_qscore_multi(QBatch B, QMultiWork M)
+{
+    const QScoreWork& W = M.w;
+    const long long lt = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (lt >= W.nTasks) return;
+    const long long t = W.taskList ? W.taskList[lt] : W.taskBase + lt;
+    int r;
+    long long mi;
+    if (W.nWork > 0) {   // batched round: decode (item, mutation, read) from the task number
+        int lo = 0, hi = W.nWork;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (W.wTaskStart[mid] <= t) lo = mid; else hi = mid;
+        }
+        const long long local = t - W.wTaskStart[lo];
+        const int nr = W.wNReads[lo];
+        r = W.readList[W.wReadBase[lo] + (int)(local % nr)];
+        mi = W.wMutBase[lo] + local / nr;
+        if (!W.rActive[r]) {
+            W.delta[t] = __builtin_nanf("");
+            return;
+        }
+    } else {
+        r = W.taskRead[t];
+        mi = W.taskMut[t];
+    }
+    const QMutRec mu = M.muts[mi];
+    const int type = mu.type;
+    int ms = mu.start, me = mu.end, nb = mu.nBases;
+    unsigned long long bases = mu.bases;
+    const int ts = B.rTs[r], te = B.rTe[r];
+    const bool scores = W.raw || ((type == 0) ? (ts < ms && me <= te) : (ts < me && ms < te));   // ReadScoresMutation
+    if (!scores || nb < 0 || nb > kQMaxBases) {
+        W.delta[t] = __builtin_nanf("");
+        return;
+    }
+    ReadView v = read_view(B, r);
+    // OrientedMutation: clip a wide mutation to the window (a substitution's bases with it), then orient
+    if (!W.raw && me - ms > 1) {
+        const int cs = max(ms, ts), ce = min(me, te);
+        if (type == 2) {
+            bases >>= 8 * (cs - ms);
+            nb = ce - cs;
+            bases &= (1ull << (8 * nb)) - 1ull;
+        }
+        ms = cs;
+        me = ce;
+    }
+    int os, oe;
+    if (W.raw) { os = ms; oe = me; }
+    else if (B.rStrand[r] == 0) { os = ms - ts; oe = me - ts; }
+    else {
+        os = te - me;
+        oe = te - ms;
+        unsigned long long rc = 0;
+        for (int k = 0; k < nb; ++k) rc |= comp_base((bases >> (8 * (nb - 1 - k))) & 0xffull) << (8 * k);
+        bases = rc;
+    }
+    const QBand a = arena(v, B.rCurA[r]);
+    const QBand b = arena(v, 2 + B.rCurB[r]);
+    const int J = v.ev.J();   // unmutated window length
+    const int width = oe - os;
+    const int lengthDiff = (type == 0) ? nb : (type == 1) ? -width : 0;
+    const int betaLinkCol = 1 + oe;
+    const int absLinkCol = 1 + oe + lengthDiff;
+    const bool atBegin = os < 3;
+    const bool atEnd = oe > J - 2;
+    QEvalWide e;
+    e.r = v.ev.r;
+    e.p = v.ev.p;
+    e.t.base = v.ev.t.base;
+    e.t.editPos = os;
+    e.t.nIns = (type == 1) ? 0 : nb;
+    e.t.nDel = (type == 0) ? 0 : width;
+    e.t.bases = bases;
+    e.t.len = J + lengthDiff;
+    const int newLen = e.t.len;
+    __shared__ int2 sxr[64][kQExtendColumns];
+    __shared__ int sxo[64][kQExtendColumns];
+    int2* xr = sxr[threadIdx.x];
+    int* xo = sxo[threadIdx.x];
+    QBand ext;
+    ext.range = xr;
+    ext.off = xo;
+    ext.cols = kQExtendColumns;
+    const int I = e.I();
+    auto alloc = [&](long long n) -> bool {
+        const unsigned long long at = atomicAdd(W.scratchTop, (unsigned long long)n);
+        if (at + n > W.scratchCap) {
+            atomicOr(W.overflow, 1);
+            return false;
+        }
+        ext.val = W.scratch + at;
+        ext.cap = n;
+        return true;
+    };
+    auto refuse = [&]() {   // the host's column check lets no such task through
+        atomicOr(W.overflow, 2);
+        W.delta[t] = __builtin_nanf("");
+    };
+    bool ovf = false;
+    float score;
+    if (os < 0 || oe > J || oe < os) { refuse(); return; }
+    if (!atBegin && !atEnd) {
+        const int extStart = (type == 1) ? os - 1 : os;
+        const int extLen = (type == 1) ? 2 : 1 + nb;
+        if (extLen > kQExtendColumns) { refuse(); return; }
+        long long need = 0;
+        for (int c = 0; c < extLen; ++c) {
+            const int j = extStart + c;
+            need += (j < a.cols) ? (a.range[j].y - a.range[j].x) : (I + 1 - a.range[a.cols - 1].x);
+        }
+        if (!alloc(max(need, 1LL))) { W.delta[t] = __builtin_nanf(""); return; }
+        if (e.p->simple) extend_alpha_simple(e, a, extStart, ext, extLen, ovf);
+        else extend_alpha(e, a, extStart, ext, extLen, ovf);
+        score = link_alpha_beta(e, ext, extLen, b, betaLinkCol, absLinkCol);
+    } else if (!atBegin && atEnd) {
+        const int extStart = os - 1;
+        const int extLen = newLen - extStart + 1;
+        if (extLen > kQExtendColumns || extLen < 1) { refuse(); return; }
+        if (!alloc((long long)extLen * (I + 1))) { W.delta[t] = __builtin_nanf(""); return; }
+        if (e.p->simple) extend_alpha_simple(e, a, extStart, ext, extLen, ovf);
+        else extend_alpha(e, a, extStart, ext, extLen, ovf);
+        score = ext.Get(I, extLen - 1);
+    } else if (atBegin && !atEnd) {
+        const int extLast = oe;
+        const int extLen = oe + lengthDiff + 1;
+        if (extLen > kQExtendColumns || extLen < 1) { refuse(); return; }
+        if (!alloc((long long)extLen * (I + 1))) { W.delta[t] = __builtin_nanf(""); return; }
+        extend_beta(e, b, extLast, ext, extLen, lengthDiff, ovf);
+        score = ext.Get(0, 0);
+    } else {
+        // whole fill of the mutated window (tiny windows only)
+        if (newLen + 1 > kQExtendColumns || newLen < 0) { refuse(); return; }
+        if (!alloc((long long)(newLen + 1) * (I + 1))) { W.delta[t] = __builtin_nanf(""); return; }
+        ext.cols = newLen + 1;
+        for (int j = 0; j < ext.cols; ++j) xr[j] = make_int2(0, 0);
+        fill_alpha(e, nullptr, nullptr, ext, nullptr, false, ovf);
+        score = ext.Get(I, newLen);
+    }
+    if (ovf) atomicOr(W.overflow, 1);
+    W.delta[t] = W.raw ? score : score - B.rScore[r];
+}
+
 // ---- k_qreduce: Score / FastIsFavorable of a batched round, one lane per mutation ----------------------
 __global__ void __launch_bounds__(256) k_qreduce(QReduceWork W)
 {
@@ -2364,6 +2525,12 @@ void launch_qscore(const QBatch& B, const QScoreWork& W, hipStream_t s)
 {
     if (W.nTasks <= 0) return;
     hipLaunchKernelGGL(k_qscore, dim3((unsigned)((W.nTasks + 63) / 64)), dim3(64), 0, s, B, W);
+}
+
+void launch_qscore_multi(const QBatch& B, const QMultiWork& W, hipStream_t s)
+{
+    if (W.w.nTasks <= 0) return;
+    hipLaunchKernelGGL(k_qscore_multi, dim3((unsigned)((W.w.nTasks + 63) / 64)), dim3(64), 0, s, B, W);
 }
 
 void launch_qscore_mid(const QBatch& B, const QMidWork& W, long long nWaves, hipStream_t s)

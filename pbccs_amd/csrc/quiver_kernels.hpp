@@ -83,6 +83,23 @@ struct QScoreWork {
     const long long* taskList = nullptr;
 };
 
+// A mutation of any width for k_qscore_multi, in template coordinates (raw: the read's window coordinates).
+// Base k of the new bases is byte k of `bases`; at most kQMaxBases of them, so that an insertion's
+// 1 + nBases extension columns fit the 8-column extend buffer (EXTEND_BUFFER_COLUMNS).
+constexpr int kQMaxBases = 7;
+constexpr int kQExtendColumns = 8;
+struct QMutRec {
+    int type;      // 0 insertion, 1 deletion, 2 substitution
+    int start, end;
+    int nBases;    // 0 for deletions
+    unsigned long long bases;
+};
+// k_qscore_multi's work: k_qscore's three forms, with taskMut / wMutBase indexing muts instead of codes
+struct QMultiWork {
+    QScoreWork w;
+    const QMutRec* muts;
+};
+
 // Batched middle-case scoring (k_qscore_mid): one wavefront per (item, read, 64-mutation chunk), the lanes
 // on consecutive mutations of the item's list -- adjacent template positions of one read, so the wave walks
 // a handful of neighbouring band columns and the same QV-feature rows, staged in LDS.  Item w owns waves
@@ -150,6 +167,7 @@ void launch_qfill_coop(const QBatch& B, const int* reads, int n, int maxRows, in
 // SparseSse reads; a read with a taller column comes back kQTall and is refilled by k_qfill_coop.
 void launch_qfill_grp(const QBatch& B, const int* reads, int n, hipStream_t s);
 void launch_qscore(const QBatch& B, const QScoreWork& W, hipStream_t s);
+void launch_qscore_multi(const QBatch& B, const QMultiWork& W, hipStream_t s);
 void launch_qscore_mid(const QBatch& B, const QMidWork& W, long long nWaves, hipStream_t s);
 void launch_qreduce(const QReduceWork& W, hipStream_t s);
 // QvEvaluator (Quiver/QvEvaluator.hpp:90-317) on one read's features against `tpl`: Inc, Del, Extra and Merge at the

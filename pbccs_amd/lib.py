@@ -23,6 +23,17 @@ class CMutation(ctypes.Structure):
     _fields_ = [("type", ctypes.c_int), ("start", ctypes.c_int), ("end", ctypes.c_int), ("new_base", ctypes.c_char)]
 
 
+class CMutationEx(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int), ("start", ctypes.c_int), ("end", ctypes.c_int),
+                ("new_bases", ctypes.c_char_p), ("n_bases", ctypes.c_int)]
+
+
+class CRepeatOptions(ctypes.Structure):
+    _fields_ = [("repeat_length", ctypes.c_int), ("min_repeat_elements", ctypes.c_int),
+                ("max_iterations", ctypes.c_int), ("mutation_separation", ctypes.c_int),
+                ("mutation_neighborhood", ctypes.c_int)]
+
+
 class CArrowConfig(ctypes.Structure):
     _fields_ = [("snr", ctypes.c_double * 4), ("score_diff", ctypes.c_double),
                 ("fast_score_threshold", ctypes.c_double), ("add_threshold", ctypes.c_double)]
@@ -148,6 +159,7 @@ PD = ctypes.POINTER(ctypes.c_double)
 PLL = ctypes.POINTER(ctypes.c_longlong)
 PM = ctypes.POINTER(CMutation)
 PF = ctypes.POINTER(ctypes.c_float)
+PMX = ctypes.POINTER(CMutationEx)
 SIGNATURES = {
     "pbccs_engine_create": (I, [I, ctypes.POINTER(P)]),
     "pbccs_engine_destroy": (None, [P]),
@@ -210,6 +222,18 @@ SIGNATURES = {
     "pbccs_quiver_polish_batch": (I, [P, ctypes.POINTER(CQuiverConfig), ctypes.POINTER(ctypes.c_char_p), I,
                                       ctypes.POINTER(CQuiverZmw), I, ctypes.POINTER(CRefineOptions),
                                       ctypes.POINTER(CQuiverResult)]),
+    # Quiver: mutations of any width and repeat refinement
+    "pbccs_quiver_scorer_score_many_ex": (I, [P, PMX, I, I, PF]),
+    "pbccs_quiver_scorer_scores_ex": (I, [P, PMX, ctypes.c_float, PF]),
+    "pbccs_quiver_scorer_is_favorable_ex": (I, [P, PMX, I, PI]),
+    "pbccs_quiver_scorer_read_score_mutation_ex": (I, [P, I, PMX, PF]),
+    "pbccs_quiver_scorer_apply_mutations_ex": (I, [P, PMX, I]),
+    "pbccs_quiver_refine_repeats": (I, [P, ctypes.POINTER(CRepeatOptions), PLL, PLL, PI]),
+    "pbccs_repeat_mutations": (I, [ctypes.c_char_p, I, I, I, I, I, PMX, I, PI]),
+    "pbccs_apply_mutations": (I, [ctypes.c_char_p, I, PMX, I, ctypes.c_char_p, I, PI, PI]),
+    "pbccs_quiver_polish_batch_ex": (I, [P, ctypes.POINTER(CQuiverConfig), ctypes.POINTER(ctypes.c_char_p), I,
+                                         ctypes.POINTER(CQuiverZmw), I, ctypes.POINTER(CRefineOptions),
+                                         ctypes.POINTER(CRepeatOptions), PLL, PLL, ctypes.POINTER(CQuiverResult)]),
     # POA draft
     "pbccs_poa_batch": (I, [P, ctypes.POINTER(CPoaInput), I, ctypes.c_longlong, I, ctypes.POINTER(CPoaOutput)]),
     "pbccs_sparse_poa_create": (I, [P, ctypes.POINTER(P)]),

@@ -233,8 +233,18 @@ class QuiverMultiReadMutationScorer:
             float("nan") if threshold is None else threshold, ctypes.byref(active)))
         return bool(active.value)
 
+    @staticmethod
+    def _wide(muts):
+        return any(not m.is_single_base() for m in muts)
+
     def ScoreMany(self, muts, fast=False):
         n = len(muts)
+        if self._wide(muts):   # mutations of any width: k_qscore_multi (single-base ones ride along)
+            cs = [m._cx() for m in muts]   # keeps the base strings alive over the call
+            arr = (_lib_mod.CMutationEx * n)(*cs)
+            out = (ctypes.c_float * n)()
+            _lib_mod.check(load().pbccs_quiver_scorer_score_many_ex(self._h, arr, n, 1 if fast else 0, out))
+            return list(out[:n])
         arr = (_lib_mod.CMutation * max(1, n))(*[m._c() for m in muts])
         out = (ctypes.c_float * max(1, n))()
         _lib_mod.check(load().pbccs_quiver_scorer_score_many(self._h, arr, n, 1 if fast else 0, out))
@@ -249,29 +259,47 @@ class QuiverMultiReadMutationScorer:
     def ReadScoreMutation(self, i, m):
         """MutationScorer::ScoreMutation on read i's scorer (read coordinates, absolute score)."""
         v = ctypes.c_float()
+        if self._wide([m]):
+            c = m._cx()
+            _lib_mod.check(load().pbccs_quiver_scorer_read_score_mutation_ex(self._h, i, ctypes.byref(c),
+                                                                              ctypes.byref(v)))
+            return v.value
         c = m._c()
         _lib_mod.check(load().pbccs_quiver_scorer_read_score_mutation(self._h, i, ctypes.byref(c), ctypes.byref(v)))
         return v.value
 
     def Scores(self, m, unscored_value=0.0):
         out = (ctypes.c_float * max(1, self.NumReads()))()
+        if self._wide([m]):
+            c = m._cx()
+            _lib_mod.check(load().pbccs_quiver_scorer_scores_ex(self._h, ctypes.byref(c), unscored_value, out))
+            return list(out[: self.NumReads()])
         c = m._c()
         _lib_mod.check(load().pbccs_quiver_scorer_scores(self._h, ctypes.byref(c), unscored_value, out))
         return list(out[: self.NumReads()])
 
-    def IsFavorable(self, m):
+    def _is_favorable(self, m, fast):
         v = ctypes.c_int()
-        c = m._c()
-        _lib_mod.check(load().pbccs_quiver_scorer_is_favorable(self._h, ctypes.byref(c), 0, ctypes.byref(v)))
+        if self._wide([m]):
+            c = m._cx()
+            _lib_mod.check(load().pbccs_quiver_scorer_is_favorable_ex(self._h, ctypes.byref(c), fast, ctypes.byref(v)))
+        else:
+            c = m._c()
+            _lib_mod.check(load().pbccs_quiver_scorer_is_favorable(self._h, ctypes.byref(c), fast, ctypes.byref(v)))
         return bool(v.value)
+
+    def IsFavorable(self, m):
+        return self._is_favorable(m, 0)
 
     def FastIsFavorable(self, m):
-        v = ctypes.c_int()
-        c = m._c()
-        _lib_mod.check(load().pbccs_quiver_scorer_is_favorable(self._h, ctypes.byref(c), 1, ctypes.byref(v)))
-        return bool(v.value)
+        return self._is_favorable(m, 1)
 
     def ApplyMutations(self, muts):
+        if self._wide(muts):
+            cs = [m._cx() for m in muts]
+            arr = (_lib_mod.CMutationEx * len(muts))(*cs)
+            _lib_mod.check(load().pbccs_quiver_scorer_apply_mutations_ex(self._h, arr, len(muts)))
+            return
         arr = (_lib_mod.CMutation * max(1, len(muts)))(*[m._c() for m in muts])
         _lib_mod.check(load().pbccs_quiver_scorer_apply_mutations(self._h, arr, len(muts)))
 
@@ -336,6 +364,79 @@ def RefineConsensus(mms, max_iterations=40, mutation_separation=10, mutation_nei
     _lib_mod.check(load().pbccs_quiver_refine_consensus(mms._h, ctypes.byref(o), ctypes.byref(nt), ctypes.byref(na),
                                                         ctypes.byref(conv)))
     return bool(conv.value), nt.value, na.value
+
+
+class RepeatMutationEnumerator:
+    """RepeatMutationEnumerator (MutationEnumerator.cpp:148-218): per run of at least min_repeat_elements copies of
+    a repeat_length element, the insertion and the deletion of one element at the run's start.  Host only."""
+
+    def __init__(self, tpl, repeat_length, min_repeat_elements=3):
+        self._tpl, self._len, self._min = tpl, repeat_length, min_repeat_elements
+
+    def Mutations(self, begin=None, end=None):
+        from . import Mutation
+        b = 0 if begin is None else begin
+        e = len(self._tpl) if end is None else end
+        t = self._tpl.encode()
+        cap = 2 * len(t) + 2
+        out = (_lib_mod.CMutationEx * cap)()
+        n = ctypes.c_int()
+        _lib_mod.check(load().pbccs_repeat_mutations(t, len(t), self._len, self._min, b, e, out, cap, ctypes.byref(n)))
+        res = []
+        for k in range(n.value):
+            m = out[k]
+            if m.type == 0:
+                res.append(Mutation(0, m.start, self._tpl[m.start:m.start + m.n_bases]))
+            else:
+                res.append(Mutation(m.type, m.start, "-", end=m.end))
+        return res
+
+
+class DinucleotideRepeatMutationEnumerator(RepeatMutationEnumerator):
+    """DinucleotideRepeatMutationEnumerator (MutationEnumerator.cpp:221-224)."""
+
+    def __init__(self, tpl, min_dinuc_repeat_elements=3):
+        super().__init__(tpl, 2, min_dinuc_repeat_elements)
+
+
+def UniqueNearbyMutations(enumerator, centers, neighborhood_size):
+    """UniqueNearbyMutations (MutationEnumerator-inl.hpp:50-68): std::set order of the union of
+    Mutations(c - n, c + n) over the centres' starts."""
+    muts = set()
+    for c in centers:
+        muts.update(enumerator.Mutations(c.start - neighborhood_size, c.start + neighborhood_size))
+    return sorted(muts)
+
+
+def ApplyMutations(muts, tpl):
+    """ApplyMutations (Mutation.cpp:115-128) and TargetToQueryPositions (Mutation.cpp:193-197) for mutations of
+    any width: (mutated template, mtp with len(tpl) + 1 entries).  Host only."""
+    t = tpl.encode()
+    n = len(muts)
+    cs = [m._cx() for m in muts]
+    arr = (_lib_mod.CMutationEx * max(1, n))(*cs)
+    cap = len(t) + sum(len(m.new_bases) for m in muts) + 1
+    out = ctypes.create_string_buffer(cap)
+    ln = ctypes.c_int()
+    mtp = (ctypes.c_int * (len(t) + 1))()
+    _lib_mod.check(load().pbccs_apply_mutations(t, len(t), arr, n, out, cap, ctypes.byref(ln), mtp))
+    return out.raw[:ln.value].decode(), list(mtp)
+
+
+def RefineRepeats(mms, repeat_length, min_repeat_elements=3, max_iterations=1, mutation_separation=10,
+                  mutation_neighborhood=20):
+    """RefineRepeats (Consensus.hpp:69-76): AbstractRefineConsensus over RepeatMutationEnumerator.  The reference's
+    RefineRepeatOptions leaves separation and neighbourhood unset; the defaults are DefaultRefineOptions'."""
+    o = _lib_mod.CRepeatOptions(repeat_length, min_repeat_elements, max_iterations, mutation_separation,
+                                mutation_neighborhood)
+    nt, na, conv = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_int()
+    _lib_mod.check(load().pbccs_quiver_refine_repeats(mms._h, ctypes.byref(o), ctypes.byref(nt), ctypes.byref(na),
+                                                      ctypes.byref(conv)))
+    return bool(conv.value), nt.value, na.value
+
+
+def RefineDinucleotideRepeats(mms, min_elements=3):
+    return RefineRepeats(mms, 2, min_elements)
 
 
 def ConsensusQVs(mms):
@@ -469,15 +570,25 @@ class PreparedQuiverBatch:
         self.__dict__.update(dict(keep=keep, carr=carr, names=names, nc=nc, cz=cz, res=res, n=n, cap=cap,
                                   cstart=cstart, cons=cons, qvb=qvb, qvs=qvs))
 
-    def run(self, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, engine=None):
+    def run(self, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, engine=None, repeats=None):
         from . import default_engine
         eng = engine or default_engine()
         carr, names, nc, cz, res, n = self.carr, self.names, self.nc, self.cz, self.res, self.n
         cap, cstart, cons, qvb, qvs = self.cap, self.cstart, self.cons, self.qvb, self.qvs
         o = _lib_mod.CRefineOptions(max_iterations, mutation_separation, mutation_neighborhood)
-        _lib_mod.check(load().pbccs_quiver_polish_batch(
-            eng._h, carr, names, nc, ctypes.cast(cz.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverZmw)), n,
-            ctypes.byref(o), ctypes.cast(res.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverResult))))
+        rep_t = rep_a = None
+        if repeats is None:
+            _lib_mod.check(load().pbccs_quiver_polish_batch(
+                eng._h, carr, names, nc, ctypes.cast(cz.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverZmw)), n,
+                ctypes.byref(o), ctypes.cast(res.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverResult))))
+        else:   # (repeat_length, min_repeat_elements[, max_iterations[, separation[, neighbourhood]]])
+            ro = _lib_mod.CRepeatOptions(*(tuple(repeats) + (3, 1, 10, 20)[len(repeats) - 1:]))
+            rep_t = (ctypes.c_longlong * max(1, n))()
+            rep_a = (ctypes.c_longlong * max(1, n))()
+            _lib_mod.check(load().pbccs_quiver_polish_batch_ex(
+                eng._h, carr, names, nc, ctypes.cast(cz.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverZmw)), n,
+                ctypes.byref(o), ctypes.byref(ro), rep_t, rep_a,
+                ctypes.cast(res.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverResult))))
         # per-field columns as Python lists once (not one structured-record access per field per ZMW)
         lens, oks = res["consensus_len"][:n].tolist(), res["ok"][:n].tolist()
         tested, applied = res["n_tested"][:n].tolist(), res["n_applied"][:n].tolist()
@@ -495,17 +606,21 @@ class PreparedQuiverBatch:
                         "qvs": qvb[c0:c0 + ln].tolist() if qvs and ok else None,
                         "n_tested": tested[k], "n_applied": applied[k],
                         "converged": bool(conv[k]), "ok": ok, "n_active": active[k]})
+            if rep_t is not None:
+                out[-1]["repeat_tested"] = rep_t[k]
+                out[-1]["repeat_applied"] = rep_a[k]
         return out
 
 
 def polish_batch(zmws, configs, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, qvs=True,
-                 engine=None):
+                 engine=None, repeats=None):
     """Many Quiver scorers at once (pbccs_quiver_polish_batch): per ZMW, create the scorer over `configs`,
     AddRead every read, RefineConsensus and (qvs) ConsensusQVs -- the per-scorer call sequence, with the
     scorers' rounds in lock-step on the device.
 
     zmws: [{"tpl", "reads": [{"seq", "strand", "ts", "te", "features": {ins, subs, del, del_tag, merge},
     "chemistry"?}]}].  Returns per ZMW {"consensus", "qvs", "n_tested", "n_applied", "converged", "ok",
-    "n_active"}."""
+    "n_active"}.  repeats=(repeat_length, min_repeat_elements) runs RefineRepeats between the two
+    (pbccs_quiver_polish_batch_ex) and adds "repeat_tested" / "repeat_applied"."""
     return PreparedQuiverBatch(zmws, configs, qvs).run(max_iterations, mutation_separation, mutation_neighborhood,
-                                                        engine)
+                                                        engine, repeats)
