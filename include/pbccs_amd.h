@@ -462,6 +462,54 @@ int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* c
                                  const pbccs_repeat_options* repeats, long long* repeat_tested,
                                  long long* repeat_applied, pbccs_quiver_result* out);
 
+/* ---- Diploid site calling (ConsensusCore Arrow/Diploid.cpp:94-241, Quiver/Diploid.cpp) -----------------
+ * A site's scores are n_reads x 9 floats, rows in AddRead order (inactive reads included), columns
+ * Scores(Substitution(p, "ACGT"[c]), 0) for c = 0..3 (the template base's own column is exactly 0),
+ * Scores(Insertion(p, "ACGT"[c - 4]), 0) for c = 4..7 and Scores(Deletion(p), 0) for c = 8 -- the order
+ * LENGTH_DIFFS (Diploid.cpp:99) assumes.  A read that is inactive or does not score a mutation contributes 0;
+ * Arrow's doubles are rounded to float.  The site tensor of [begin, end) is [end - begin][n_reads][9]. */
+typedef struct {
+    int position;             /* template position of the site */
+    int allele0;              /* DiploidSite::Allele0 / Allele1: column indices 0..8 */
+    int allele1;
+    float log_bayes_factor;   /* DiploidSite::LogBayesFactor */
+} pbccs_diploid_site;
+
+/* DiploidSite* IsSiteHeterozygous(const float* siteScores, int dim1, int dim2, float logPriorRatio)
+ *                                                                                  (Diploid.cpp:219-239)
+ * Host-only (no engine or device needed): float arithmetic in the reference's order with the host libm.
+ * *is_het = (logBF - log_prior_ratio > 0); site (allele0, allele1, log_bayes_factor; position untouched) and
+ * allele_for_read (n_reads entries, AssignReadsToAlleles :204-213) are written either way.
+ * n_alleles != 9, n_reads <= 0 or a null pointer: PBCCS_EINVAL (the reference only asserts). */
+int pbccs_is_site_heterozygous(const float* site_scores, int n_reads, int n_alleles, float log_prior_ratio,
+                               int* is_het, pbccs_diploid_site* site, int* allele_for_read);
+
+/* The site tensor of template positions [begin, end), scored on the device (8 mutations per site through the
+ * scorer's scoring round, no fast threshold).  *n = the float count (end - begin) * NumReads() * 9;
+ * PBCCS_ERANGE when cap is smaller (out may be NULL with cap 0 to size the call).  begin < 0, end >
+ * TemplateLength or begin >= end: PBCCS_EINVAL before any launch; the scorer stays usable. */
+int pbccs_scorer_site_scores(pbccs_scorer* s, int begin, int end, float* out, long long cap, long long* n);
+int pbccs_quiver_scorer_site_scores(pbccs_quiver_scorer* s, int begin, int end, float* out, long long cap,
+                                    long long* n);
+/* IsSiteHeterozygous over every site of [begin, end): the device screens each site (k_diploid) and leaves to
+ * the host primitive above every site that is heterozygous or lies within the screen's bound of being so, so
+ * each reported site is pbccs_is_site_heterozygous' answer on the tensor pbccs_scorer_site_scores returns.
+ * host_all != 0 sends every site to the host (same results).  Sites in ascending position; *n = their count,
+ * PBCCS_ERANGE when it exceeds cap (nothing is written).  allele_for_read (may be NULL): cap x NumReads()
+ * ints, row k for sites[k].  A scorer without reads reports no site. */
+int pbccs_scorer_diploid_sites(pbccs_scorer* s, int begin, int end, float log_prior_ratio, int host_all,
+                               pbccs_diploid_site* sites, int cap, int* n, int* allele_for_read);
+int pbccs_quiver_scorer_diploid_sites(pbccs_quiver_scorer* s, int begin, int end, float log_prior_ratio,
+                                      int host_all, pbccs_diploid_site* sites, int cap, int* n,
+                                      int* allele_for_read);
+/* The screen's work since the last reset */
+typedef struct {
+    long long sites_screened;      /* sites k_diploid looked at */
+    long long sites_sent_to_host;  /* ... whose slices were downloaded and decided by the host primitive */
+    long long sites_reported;      /* ... reported heterozygous */
+} pbccs_diploid_stats;
+int pbccs_diploid_stats_get(pbccs_engine* eng, pbccs_diploid_stats* out, int reset);
+
 /* ---- POA draft (pbccs src/SparsePoa.cpp, ConsensusCore/src/C++/Poa) ---------------------------------
  * The read-vs-graph DP and its traceback run on the device (k_poa_fill / k_poa_trace); the graph lives on
  * the host.  Scores use DefaultPoaConfig (match 3, mismatch -5, insert -4, delete -4). */

@@ -214,6 +214,61 @@ public:
     }
 };
 
+// DiploidSite / IsSiteHeterozygous (Arrow/Diploid.hpp:47-62, Diploid.cpp:94-241).  Position is this facade's
+// addition: the template position, set by the scorers' DiploidSites (-1 from IsSiteHeterozygous).
+struct DiploidSite {
+    int Allele0;
+    int Allele1;
+    float LogBayesFactor;
+    std::vector<int> AlleleForRead;
+    int Position;
+    DiploidSite(int allele0, int allele1, float logBayesFactor, std::vector<int> alleleForRead)
+        : Allele0(allele0), Allele1(allele1), LogBayesFactor(logBayesFactor), AlleleForRead(std::move(alleleForRead)),
+          Position(-1)
+    {}
+};
+
+// siteScores: dim1 reads x dim2 (= 9) alleles, row-major.  NULL when the site is not heterozygous; otherwise a
+// new DiploidSite the caller owns, as in the reference.
+inline DiploidSite* IsSiteHeterozygous(const float* siteScores, int dim1, int dim2, float logPriorRatio)
+{
+    int isHet = 0;
+    pbccs_diploid_site site;
+    std::vector<int> alleleForRead(dim1 > 0 ? dim1 : 0);
+    detail::Check(pbccs_is_site_heterozygous(siteScores, dim1, dim2, logPriorRatio, &isHet, &site, alleleForRead.data()));
+    if (!isHet) return nullptr;
+    return new DiploidSite(site.allele0, site.allele1, site.log_bayes_factor, alleleForRead);
+}
+
+namespace diploid {
+// the scorers' SiteScores / DiploidSites over either family's C entry points
+template <class H, class F>
+std::vector<float> SiteScores(H* handle, F call, int nReads, int begin, int end)
+{
+    std::vector<float> out((size_t)(end > begin ? end - begin : 0) * (size_t)nReads * 9);
+    long long n = 0;
+    detail::Check(call(handle, begin, end, out.data(), (long long)out.size(), &n));
+    return out;
+}
+template <class H, class F>
+std::vector<DiploidSite> DiploidSites(H* handle, F call, int nReads, int begin, int end, float logPriorRatio,
+                                      bool hostAll)
+{
+    const int cap = end > begin ? end - begin : 0;
+    std::vector<pbccs_diploid_site> sites((size_t)cap + 1);
+    std::vector<int> afr((size_t)cap * (size_t)nReads + 1);
+    int n = 0;
+    detail::Check(call(handle, begin, end, logPriorRatio, hostAll ? 1 : 0, sites.data(), cap, &n, afr.data()));
+    std::vector<DiploidSite> out;
+    for (int k = 0; k < n; ++k) {
+        out.emplace_back(sites[k].allele0, sites[k].allele1, sites[k].log_bayes_factor,
+                         std::vector<int>(afr.begin() + (size_t)k * nReads, afr.begin() + (size_t)(k + 1) * nReads));
+        out.back().Position = sites[k].position;
+    }
+    return out;
+}
+}  // namespace diploid
+
 class ArrowMultiReadMutationScorer {
 public:
     ArrowMultiReadMutationScorer(const ArrowConfig& config, const std::string& tpl)
@@ -303,6 +358,18 @@ public:
         std::vector<int> out(NumReads());
         detail::Check(pbccs_scorer_num_flipflops(handle_, out.data()));
         return out;
+    }
+    // The site tensor of template positions [begin, end) (end < 0: the template's end): [site][read][9] floats,
+    // a site's slice being what IsSiteHeterozygous takes; and IsSiteHeterozygous at each of those positions
+    // (the heterozygous sites by ascending Position).
+    std::vector<float> SiteScores(int begin = 0, int end = -1)
+    {
+        return diploid::SiteScores(handle_, pbccs_scorer_site_scores, NumReads(), begin, end < 0 ? TemplateLength() : end);
+    }
+    std::vector<DiploidSite> DiploidSites(float logPriorRatio, int begin = 0, int end = -1, bool hostAll = false)
+    {
+        return diploid::DiploidSites(handle_, pbccs_scorer_diploid_sites, NumReads(), begin,
+                                    end < 0 ? TemplateLength() : end, logPriorRatio, hostAll);
     }
     pbccs_scorer* Handle() { return handle_; }
 

@@ -298,6 +298,11 @@ typedef QvRecursorType<PBCCS_QV_RECURSOR_DENSE_SSE, true> SseQvSumProductRecurso
 typedef QvRecursorType<PBCCS_QV_RECURSOR_DENSE_SIMPLE, false> SimpleQvRecursor;
 typedef QvRecursorType<PBCCS_QV_RECURSOR_DENSE_SIMPLE, true> SimpleQvSumProductRecursor;
 
+// DiploidSite / IsSiteHeterozygous (Quiver/Diploid.hpp:47-62): the Quiver and Arrow implementations differ only in
+// casts (Quiver/Diploid.cpp, Arrow/Diploid.cpp), so the two namespaces share one definition
+using Arrow::DiploidSite;
+using Arrow::IsSiteHeterozygous;
+
 // AbstractMultiReadMutationScorer (Quiver/MultiReadMutationScorer.hpp:55-124)
 class AbstractMultiReadMutationScorer {
 public:
@@ -495,6 +500,18 @@ public:
         return std::make_pair(t, q);
     }
     pbccs_quiver_scorer* Handle() const override { return handle_; }
+    // The site tensor of template positions [begin, end) (end < 0: the template's end), [site][read][9] floats, and
+    // IsSiteHeterozygous at each of those positions (the heterozygous sites by ascending Position)
+    std::vector<float> SiteScores(int begin = 0, int end = -1) const
+    {
+        return Arrow::diploid::SiteScores(handle_, pbccs_quiver_scorer_site_scores, NumReads(), begin,
+                                  end < 0 ? TemplateLength() : end);
+    }
+    std::vector<DiploidSite> DiploidSites(float logPriorRatio, int begin = 0, int end = -1, bool hostAll = false) const
+    {
+        return Arrow::diploid::DiploidSites(handle_, pbccs_quiver_scorer_diploid_sites, NumReads(), begin,
+                                    end < 0 ? TemplateLength() : end, logPriorRatio, hostAll);
+    }
 
 private:
     float ScoreOne(const Mutation& m, bool fast) const

@@ -141,6 +141,12 @@ class Engine:
         return {k: (list(getattr(c, k)) if k in ("fill_work", "uncertain_why") else getattr(c, k))
                 for k, _ in _lib_mod.CCounters._fields_}
 
+    def diploid_stats(self, reset=False):
+        """The diploid screen's work: sites_screened, sites_sent_to_host, sites_reported."""
+        c = _lib_mod.CDiploidStats()
+        _lib_mod.check(load().pbccs_diploid_stats_get(self._h, ctypes.byref(c), 1 if reset else 0))
+        return {k: getattr(c, k) for k, _ in _lib_mod.CDiploidStats._fields_}
+
 
 _default_engine = None
 
@@ -253,6 +259,18 @@ class ArrowMultiReadMutationScorer:
         _lib_mod.check(load().pbccs_scorer_num_flipflops(self._h, out))
         return list(out[: self.NumReads()])
 
+    def SiteScores(self, begin=0, end=None):
+        """The site tensor of template positions [begin, end): float32 ndarray (sites, reads, 9), see diploid.py."""
+        from . import diploid
+        return diploid.site_scores(load().pbccs_scorer_site_scores, self._h, self.NumReads(), self.TemplateLength(),
+                                   begin, end)
+
+    def DiploidSites(self, log_prior_ratio, begin=0, end=None, host_all=False):
+        """IsSiteHeterozygous at every position of [begin, end): the heterozygous DiploidSites, by Position."""
+        from . import diploid
+        return diploid.diploid_sites(load().pbccs_scorer_diploid_sites, self._h, self.NumReads(),
+                                     self.TemplateLength(), log_prior_ratio, begin, end, host_all)
+
 
 def RefineConsensus(mms, max_iterations=40, mutation_separation=10, mutation_neighborhood=20):
     """bool RefineConsensus(MRMS&, size_t* nTested, size_t* nApplied, const RefineOptions&) -> (converged, nT, nA).
@@ -288,6 +306,7 @@ from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E4
                      QuiverMultiReadMutationScorer, QvEvaluator, QvSequenceFeatures, ALL_MOVES, BASIC_MOVES,
                      RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator, RefineRepeats,
                      RefineDinucleotideRepeats)
+from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -323,4 +323,62 @@ int probability_to_qv(double p)
     return static_cast<int>(std::round(-10.0 * std::log10(p)));
 }
 
+// ---- diploid site calling ------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kLengthDiffs[kSiteAlleles] = {0, 0, 0, 0, 1, 1, 1, 1, -1};   // Diploid.cpp:99
+
+inline float logaddexp_f(float x, float y)   // Diploid.cpp:110-118
+{
+    const float diff = x - y;
+    if (diff > 0) return x + log1pf(expf(-diff));
+    return y + log1pf(expf(diff));
+}
+
+}  // namespace
+
+bool is_site_heterozygous(const float* M, int I, float logPriorRatio, DiploidCall* call, int* alleleForRead)
+{
+    const int G = kSiteAlleles;
+    // HomozygousLogLikelihood (:123-132): column sums in read order, then accumulate from -FLT_MAX
+    float hom = -std::numeric_limits<float>::max();
+    for (int g = 0; g < G; ++g) {
+        float s = 0.0f;
+        for (int i = 0; i < I; ++i) s += M[(size_t)i * G + g];
+        hom = logaddexp_f(hom, s);
+    }
+    // HeterozygousLogLikelihood (:137-178): the pairs g0 < g1 of equal length difference, strict > for the best
+    const float log2f_ = (float)std::log(2.0);   // `float log2 = log(2)` (:144)
+    float totals[kSitePairs];
+    int nPairs = 0;
+    float runningMax = -std::numeric_limits<float>::max();
+    int a0 = -1, a1 = -1;
+    for (int g0 = 0; g0 < G; ++g0) {
+        for (int g1 = g0 + 1; g1 < G; ++g1) {
+            if (kLengthDiffs[g0] != kLengthDiffs[g1]) continue;
+            float total = (float)(-I) * log2f_;   // `-I * log2` (:156): int times float
+            for (int i = 0; i < I; ++i) total += logaddexp_f(M[(size_t)i * G + g0], M[(size_t)i * G + g1]);
+            totals[nPairs++] = total;
+            if (total > runningMax) {
+                runningMax = total;
+                a0 = g0;
+                a1 = g1;
+            }
+        }
+    }
+    float het = -std::numeric_limits<float>::max();
+    for (int k = 0; k < nPairs; ++k) het = logaddexp_f(het, totals[k]);
+    const float logBF = het - hom;   // :228
+    call->allele0 = a0;
+    call->allele1 = a1;
+    call->logBayesFactor = logBF;
+    const bool isHet = logBF - logPriorRatio > 0;   // :230
+    // AssignReadsToAlleles (:204-213): strict >, so a tie goes to allele 1.  With no pair above -FLT_MAX (NaN
+    // scores) the reference would index column -1; no allele is assigned here.
+    if (alleleForRead)
+        for (int i = 0; i < I; ++i)
+            alleleForRead[i] = (a0 >= 0 && M[(size_t)i * G + a0] > M[(size_t)i * G + a1]) ? 0 : 1;
+    return isHet;
+}
+
 }  // namespace pbccs

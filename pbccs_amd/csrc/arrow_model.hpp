@@ -121,4 +121,26 @@ void nearby_repeat_mutations(const std::string& tpl, int repeatLength, int minRe
 // ProbabilityToQV (Consensus-inl.hpp:130-138)
 int probability_to_qv(double p);
 
+// ---- diploid site calling (Arrow/Diploid.cpp:94-241; Quiver/Diploid.cpp differs only in casts) ------------
+// A site's scores: nReads x 9 floats, row-major, columns Substitution(p, ACGT), Insertion(p, ACGT), Deletion(p)
+// -- the order LENGTH_DIFFS (Diploid.cpp:99) assumes.
+constexpr int kSiteAlleles = 9;
+constexpr int kSitePairs = 12;   // allele pairs g0 < g1 of equal length difference: 6 substitution + 6 insertion
+struct DiploidCall {
+    int allele0 = -1, allele1 = -1;
+    float logBayesFactor = 0.0f;
+};
+// IsSiteHeterozygous (Diploid.cpp:219-239) in float with the reference's operation order and the host libm.
+// Returns logBF - logPriorRatio > 0; alleleForRead (nReads entries, may be NULL) receives AssignReadsToAlleles
+// (:204-213).  The call is filled either way.
+bool is_site_heterozygous(const float* siteScores, int nReads, float logPriorRatio, DiploidCall* call,
+                          int* alleleForRead);
+struct DiploidSiteH {   // a reported DiploidSite (Diploid.hpp), AlleleForRead kept beside it
+    int position, allele0, allele1;
+    float logBayesFactor;
+};
+struct DiploidStats {   // the device screen's work (pbccs_diploid_stats)
+    long long sitesScreened = 0, sitesSentToHost = 0, sitesReported = 0;
+};
+
 }  // namespace pbccs

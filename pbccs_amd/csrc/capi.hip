@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -49,6 +50,7 @@ struct pbccs_engine {
     int nextSlot = 0;
     std::mutex statsMu;        // counters / stats are merged from the slots' worker threads
     long long oomRetries = 0;   // device batches rerun after PBCCS_EOOM
+    DiploidStats diploid;       // the diploid screen's work (pbccs_diploid_stats_get)
     long long createHostNs = 0, createUploadNs = 0;   // pbccs_batch_create: host setup / reservations + upload
     std::vector<std::unique_ptr<Workspace>> slots;
     // the POA draft step's device state (made on first use): kPoaSlices runners, one per concurrent slice
@@ -1794,6 +1796,120 @@ int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* c
         return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
     return quiver_polish_batch_impl(eng, configs, chemistries, n_configs, zmws, n, opts, repeats, repeat_tested,
                                     repeat_applied, out);
+}
+
+// ---------------------------------------------------------------- Diploid site calling
+// IsSiteHeterozygous / DiploidSite (Arrow/Diploid.cpp:94-241, Quiver/Diploid.cpp); DESIGN.md §3.13
+
+int pbccs_is_site_heterozygous(const float* site_scores, int n_reads, int n_alleles, float log_prior_ratio,
+                               int* is_het, pbccs_diploid_site* site, int* allele_for_read)
+{
+    // the reference asserts dim2 == MUTATIONS_PER_SITE (Diploid.cpp:140)
+    if (!site_scores || !is_het || !site || !allele_for_read || n_alleles != kSiteAlleles || n_reads <= 0)
+        return fail(PBCCS_EINVAL, "bad argument");
+    DiploidCall call;
+    *is_het = is_site_heterozygous(site_scores, n_reads, log_prior_ratio, &call, allele_for_read) ? 1 : 0;
+    site->allele0 = call.allele0;
+    site->allele1 = call.allele1;
+    site->log_bayes_factor = call.logBayesFactor;
+    return PBCCS_OK;
+}
+
+// the two families' common back: range and capacity checks before any launch, then the batch's call
+static int site_scores_impl(int tplLen, int nReads, int begin, int end, float* out, long long cap, long long* n,
+                            const std::function<void(std::vector<float>*)>& run)
+{
+    if (!n) return fail(PBCCS_EINVAL, "bad argument");
+    if (begin < 0 || end > tplLen || begin >= end) return fail(PBCCS_EINVAL, "site range outside the template");
+    *n = (long long)(end - begin) * nReads * kSiteAlleles;
+    if (cap < *n || (!out && *n > 0)) return fail(PBCCS_ERANGE, "buffer too small");
+    if (*n == 0) return PBCCS_OK;
+    return guarded([&] {
+        std::vector<float> t;
+        run(&t);
+        std::copy(t.begin(), t.end(), out);
+        return PBCCS_OK;
+    });
+}
+
+static int diploid_sites_impl(pbccs_engine* eng, int tplLen, int nReads, int begin, int end,
+                              pbccs_diploid_site* sites, int cap, int* n, int* allele_for_read,
+                              const std::function<void(std::vector<DiploidSiteH>*, std::vector<int>*, DiploidStats*)>& run)
+{
+    if (!n || cap < 0 || (cap > 0 && !sites)) return fail(PBCCS_EINVAL, "bad argument");
+    if (begin < 0 || end > tplLen || begin >= end) return fail(PBCCS_EINVAL, "site range outside the template");
+    *n = 0;
+    if (nReads == 0) return PBCCS_OK;
+    return guarded([&] {
+        std::vector<DiploidSiteH> found;
+        std::vector<int> afr;
+        DiploidStats st;
+        run(&found, &afr, &st);
+        {
+            std::lock_guard<std::mutex> lock(eng->statsMu);
+            eng->diploid.sitesScreened += st.sitesScreened;
+            eng->diploid.sitesSentToHost += st.sitesSentToHost;
+            eng->diploid.sitesReported += st.sitesReported;
+        }
+        *n = (int)found.size();
+        if (*n > cap) return fail(PBCCS_ERANGE, "buffer too small");
+        for (int k = 0; k < *n; ++k) {
+            sites[k].position = found[k].position;
+            sites[k].allele0 = found[k].allele0;
+            sites[k].allele1 = found[k].allele1;
+            sites[k].log_bayes_factor = found[k].logBayesFactor;
+        }
+        if (allele_for_read) std::copy(afr.begin(), afr.end(), allele_for_read);
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_scorer_site_scores(pbccs_scorer* s, int begin, int end, float* out, long long cap, long long* n)
+{
+    if (!s) return fail(PBCCS_EINVAL, "bad argument");
+    return site_scores_impl((int)s->batch->Template(s->z).size(), s->batch->NumReads(s->z), begin, end, out, cap, n,
+                            [&](std::vector<float>* t) { s->batch->SiteScores(s->z, begin, end, t); });
+}
+
+int pbccs_quiver_scorer_site_scores(pbccs_quiver_scorer* s, int begin, int end, float* out, long long cap,
+                                    long long* n)
+{
+    if (!s) return fail(PBCCS_EINVAL, "bad argument");
+    return site_scores_impl((int)s->batch->Template(s->z).size(), s->batch->NumReads(s->z), begin, end, out, cap, n,
+                            [&](std::vector<float>* t) { s->batch->SiteScores(s->z, begin, end, t); });
+}
+
+int pbccs_scorer_diploid_sites(pbccs_scorer* s, int begin, int end, float log_prior_ratio, int host_all,
+                               pbccs_diploid_site* sites, int cap, int* n, int* allele_for_read)
+{
+    if (!s) return fail(PBCCS_EINVAL, "bad argument");
+    return diploid_sites_impl(s->eng, (int)s->batch->Template(s->z).size(), s->batch->NumReads(s->z), begin, end, sites,
+                              cap, n, allele_for_read,
+                              [&](std::vector<DiploidSiteH>* f, std::vector<int>* a, DiploidStats* st) {
+                                  s->batch->DiploidSites(s->z, begin, end, log_prior_ratio, host_all != 0, f, a, st);
+                              });
+}
+
+int pbccs_quiver_scorer_diploid_sites(pbccs_quiver_scorer* s, int begin, int end, float log_prior_ratio,
+                                      int host_all, pbccs_diploid_site* sites, int cap, int* n, int* allele_for_read)
+{
+    if (!s) return fail(PBCCS_EINVAL, "bad argument");
+    return diploid_sites_impl(s->eng, (int)s->batch->Template(s->z).size(), s->batch->NumReads(s->z), begin, end, sites,
+                              cap, n, allele_for_read,
+                              [&](std::vector<DiploidSiteH>* f, std::vector<int>* a, DiploidStats* st) {
+                                  s->batch->DiploidSites(s->z, begin, end, log_prior_ratio, host_all != 0, f, a, st);
+                              });
+}
+
+int pbccs_diploid_stats_get(pbccs_engine* eng, pbccs_diploid_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lock(eng->statsMu);
+    out->sites_screened = eng->diploid.sitesScreened;
+    out->sites_sent_to_host = eng->diploid.sitesSentToHost;
+    out->sites_reported = eng->diploid.sitesReported;
+    if (reset) eng->diploid = DiploidStats();
+    return PBCCS_OK;
 }
 
 // ---------------------------------------------------------------- POA draft

@@ -1,5 +1,6 @@
 // pbccs_amd/csrc/engine.hip -- ArrowBatch: HBM residency + orchestration of the polishing rounds.
 #include "engine.hpp"
+#include "diploid_kernels.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1917,6 +1918,47 @@ void ArrowBatch::ScoreLists(const std::vector<int>& zl, const std::vector<std::v
             (*perRead)[k].assign(d.begin() + rDeltaBase_[k], d.begin() + rDeltaBase_[k] + (long long)nr * rNMut_[k]);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Diploid site calling (Arrow/Diploid.cpp:94-241)
+// ------------------------------------------------------------------------------------------------
+const float* ArrowBatch::SiteScoresDevice(int zi, int begin, int end)
+{
+    const StreamScope bound(stream_);
+    const HZmw& z = zmws_.at(zi);
+    if (begin < 0 || end > (int)z.tpl.size() || begin >= end) throw std::invalid_argument("site range outside the template");
+    const long long per = (long long)z.nReads * kSiteAlleles;
+    dSite_.reserve((size_t)std::max<long long>(per * (end - begin), 1), false);
+    if (z.nReads == 0) return dSite_.ptr;
+    std::vector<std::vector<int>> codes(1);
+    // site_chunk() = kSiteChunk sites (8 mutations each) per scoring round, no fast threshold: every read's term is scored
+    const int chunk = site_chunk();
+    for (int b = begin; b < end; b += chunk) {
+        const int e = std::min(end, b + chunk);
+        site_mutation_codes(z.tpl, b, e, &codes[0]);
+        RunRound({zi}, &codes, -std::numeric_limits<double>::max(), false);
+        launch_site_scores_arrow(dDelta_.ptr + rDeltaBase_[0], dCodes_.ptr, pRActive_ + z.readBegin, pRTs_ + z.readBegin,
+                                 pRTe_ + z.readBegin, z.nReads, e - b, dSite_.ptr + per * (b - begin), stream_);
+        PBCCS_HIP(hipGetLastError());
+    }
+    return dSite_.ptr;
+}
+
+void ArrowBatch::SiteScores(int zi, int begin, int end, std::vector<float>* out)
+{
+    const StreamScope bound(stream_);
+    SiteScoresDevice(zi, begin, end);
+    download(*out, dSite_, (size_t)zmws_[zi].nReads * kSiteAlleles * (size_t)(end - begin), stream_);
+    PBCCS_HIP(hipStreamSynchronize(stream_));
+}
+
+void ArrowBatch::DiploidSites(int zi, int begin, int end, float logPriorRatio, bool hostAll,
+                              std::vector<DiploidSiteH>* sites, std::vector<int>* alleleForRead, DiploidStats* stats)
+{
+    const float* t = SiteScoresDevice(zi, begin, end);
+    diploid_sites(t, end - begin, zmws_[zi].nReads, begin, logPriorRatio, hostAll, diploid_, stream_, sites,
+                  alleleForRead, stats);
 }
 
 // ------------------------------------------------------------------------------------------------

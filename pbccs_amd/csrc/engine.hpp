@@ -192,6 +192,12 @@ private:
     std::vector<char*> retired_;
 };
 
+// Device scratch of the diploid screen (diploid_kernels.hpp): per-site flags, the marked sites and their packed slices
+struct DiploidScratch {
+    DevVec<int> flags, list;
+    DevVec<float> packed;
+};
+
 // Band value pool: a large virtual-address reservation whose physical backing is mapped in 1 GB
 // granules as the batch's bands grow (hipMemAddressReserve / hipMemCreate / hipMemMap).  Growth never
 // copies and never needs old + new copies side by side, so several batches can keep tens of GB of bands
@@ -387,6 +393,14 @@ public:
     void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs);
     // ApplyMutations (MultiReadMutationScorer.cpp:235-267).  Returns false on an invalid edit.
     bool ApplyMutations(int z, const std::vector<Mutation>& muts);
+    // Diploid site calling (Arrow/Diploid.cpp).  The site tensor of template positions
+    // [begin, end): [site][read][9] floats, Scores(m, 0) of Substitution / Insertion(p, ACGT) and Deletion(p)
+    // rounded to float, left on the device (valid until the next scoring call); SiteScores downloads it.
+    const float* SiteScoresDevice(int z, int begin, int end);
+    void SiteScores(int z, int begin, int end, std::vector<float>* out);
+    // IsSiteHeterozygous over the tensor: the device screen, then the host primitive on the marked sites.
+    void DiploidSites(int z, int begin, int end, float logPriorRatio, bool hostAll, std::vector<DiploidSiteH>* sites,
+                      std::vector<int>* alleleForRead, DiploidStats* stats);
 
     // ---- host queries (MultiReadMutationScorer surface) -------------------------------
     int NumZmws() const { return (int)zmws_.size(); }
@@ -551,6 +565,8 @@ private:
     bool profiling_ = false;
     DevVec<unsigned long long>& dStats_;
     DevVec<long long> dTrace_;   // PBCCS_FILL_TRACE diagnostics
+    DevVec<float> dSite_;        // the site tensor (SiteScoresDevice)
+    DiploidScratch diploid_;
     struct Pending {
         int kind;
         hipEvent_t a, b;

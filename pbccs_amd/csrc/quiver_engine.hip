@@ -18,6 +18,7 @@
 #include <unordered_set>
 
 #include "arrow_kernels.hpp"
+#include "diploid_kernels.hpp"
 
 namespace pbccs {
 namespace quiver {
@@ -647,6 +648,44 @@ void QuiverBatch::Deltas(int zi, const std::vector<int>& codes, std::vector<floa
     ScoreDeltas({zi}, {codes}, &taskStart, &mutStart);
     get(*out, dDelta_, (size_t)nt, stream_);
     QHIP(hipStreamSynchronize(stream_));
+}
+
+// ---- diploid site calling (Quiver/Diploid.cpp) ---------------------------------------------
+const float* QuiverBatch::SiteScoresDevice(int zi, int begin, int end)
+{
+    const HZmw& z = zmws_.at(zi);
+    if (begin < 0 || end > (int)z.tpl.size() || begin >= end) throw std::invalid_argument("site range outside the template");
+    const int nr = (int)z.reads.size();
+    const long long per = (long long)nr * kSiteAlleles;
+    dSite_.reserve((size_t)std::max<long long>(per * (end - begin), 1), false);
+    if (nr == 0) return dSite_.ptr;
+    std::vector<std::vector<int>> codes(1);
+    std::vector<long long> taskStart, mutStart;
+    // site_chunk() = kSiteChunk sites (8 mutations each) per scoring round; ScoreDeltas takes no fast threshold
+    const int chunk = site_chunk();
+    for (int b = begin; b < end; b += chunk) {
+        const int e = std::min(end, b + chunk);
+        site_mutation_codes(z.tpl, b, e, &codes[0]);
+        ScoreDeltas({zi}, codes, &taskStart, &mutStart);
+        launch_site_scores_quiver(dDelta_.ptr, dCodes_.ptr, nr, e - b, dSite_.ptr + per * (b - begin), stream_);
+        QHIP(hipGetLastError());
+    }
+    return dSite_.ptr;
+}
+
+void QuiverBatch::SiteScores(int zi, int begin, int end, std::vector<float>* out)
+{
+    SiteScoresDevice(zi, begin, end);
+    get(*out, dSite_, zmws_[zi].reads.size() * (size_t)kSiteAlleles * (size_t)(end - begin), stream_);
+    QHIP(hipStreamSynchronize(stream_));
+}
+
+void QuiverBatch::DiploidSites(int zi, int begin, int end, float logPriorRatio, bool hostAll,
+                               std::vector<DiploidSiteH>* sites, std::vector<int>* alleleForRead, DiploidStats* stats)
+{
+    const float* t = SiteScoresDevice(zi, begin, end);
+    diploid_sites(t, end - begin, (int)zmws_[zi].reads.size(), begin, logPriorRatio, hostAll, diploid_, stream_, sites,
+                  alleleForRead, stats);
 }
 
 void QuiverBatch::RunScore(const std::vector<int>& tr, const std::vector<int>& tm, const std::vector<int>& codes,

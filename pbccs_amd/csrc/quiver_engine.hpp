@@ -148,6 +148,13 @@ public:
     // from the read's alpha band (Viterbi configs only): the gapped target and query strings.
     bool Alignment(int r, std::string* target, std::string* query);
 
+    // Diploid site calling (Quiver/Diploid.cpp), as ArrowBatch's: the tensor holds the float
+    // deltas with 0 where a read is inactive or does not score the mutation.
+    const float* SiteScoresDevice(int z, int begin, int end);
+    void SiteScores(int z, int begin, int end, std::vector<float>* out);
+    void DiploidSites(int z, int begin, int end, float logPriorRatio, bool hostAll, std::vector<DiploidSiteH>* sites,
+                      std::vector<int>* alleleForRead, DiploidStats* stats);
+
     const std::string& Template(int z) const { return zmws_[z].tpl; }
     int NumReads(int z) const { return (int)zmws_[z].reads.size(); }
     int ReadIndex(int z, int k) const { return zmws_[z].reads[k]; }
@@ -264,6 +271,8 @@ private:
     DevVec<float> dWFast_;
     DevVec<double> dMScore_, dSelScore_;
     DevVec<unsigned char> dFav_, dSelTmp_;
+    DevVec<float> dSite_;   // the site tensor (SiteScoresDevice)
+    DiploidScratch diploid_;
 };
 
 }  // namespace quiver

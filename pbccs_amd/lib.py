@@ -150,6 +150,16 @@ class CPoaStats(ctypes.Structure):
                 ("thread_ms", ctypes.c_double), ("consensus_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
 
 
+class CDiploidSite(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_int), ("allele0", ctypes.c_int), ("allele1", ctypes.c_int),
+                ("log_bayes_factor", ctypes.c_float)]
+
+
+class CDiploidStats(ctypes.Structure):
+    _fields_ = [("sites_screened", ctypes.c_longlong), ("sites_sent_to_host", ctypes.c_longlong),
+                ("sites_reported", ctypes.c_longlong)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -234,6 +244,13 @@ SIGNATURES = {
     "pbccs_quiver_polish_batch_ex": (I, [P, ctypes.POINTER(CQuiverConfig), ctypes.POINTER(ctypes.c_char_p), I,
                                          ctypes.POINTER(CQuiverZmw), I, ctypes.POINTER(CRefineOptions),
                                          ctypes.POINTER(CRepeatOptions), PLL, PLL, ctypes.POINTER(CQuiverResult)]),
+    # Diploid site calling
+    "pbccs_is_site_heterozygous": (I, [PF, I, I, ctypes.c_float, PI, ctypes.POINTER(CDiploidSite), PI]),
+    "pbccs_scorer_site_scores": (I, [P, I, I, PF, ctypes.c_longlong, PLL]),
+    "pbccs_quiver_scorer_site_scores": (I, [P, I, I, PF, ctypes.c_longlong, PLL]),
+    "pbccs_scorer_diploid_sites": (I, [P, I, I, ctypes.c_float, I, ctypes.POINTER(CDiploidSite), I, PI, PI]),
+    "pbccs_quiver_scorer_diploid_sites": (I, [P, I, I, ctypes.c_float, I, ctypes.POINTER(CDiploidSite), I, PI, PI]),
+    "pbccs_diploid_stats_get": (I, [P, ctypes.POINTER(CDiploidStats), I]),
     # POA draft
     "pbccs_poa_batch": (I, [P, ctypes.POINTER(CPoaInput), I, ctypes.c_longlong, I, ctypes.POINTER(CPoaOutput)]),
     "pbccs_sparse_poa_create": (I, [P, ctypes.POINTER(P)]),

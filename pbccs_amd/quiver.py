@@ -357,6 +357,18 @@ class QuiverMultiReadMutationScorer:
         _lib_mod.check(load().pbccs_quiver_scorer_allocated_entries(self._h, i, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def SiteScores(self, begin=0, end=None):
+        """The site tensor of template positions [begin, end): float32 ndarray (sites, reads, 9), see diploid.py."""
+        from . import diploid
+        return diploid.site_scores(load().pbccs_quiver_scorer_site_scores, self._h, self.NumReads(),
+                                   self.TemplateLength(), begin, end)
+
+    def DiploidSites(self, log_prior_ratio, begin=0, end=None, host_all=False):
+        """IsSiteHeterozygous at every position of [begin, end): the heterozygous DiploidSites, by Position."""
+        from . import diploid
+        return diploid.diploid_sites(load().pbccs_quiver_scorer_diploid_sites, self._h, self.NumReads(),
+                                     self.TemplateLength(), log_prior_ratio, begin, end, host_all)
+
 
 def RefineConsensus(mms, max_iterations=40, mutation_separation=10, mutation_neighborhood=20):
     o = _lib_mod.CRefineOptions(max_iterations, mutation_separation, mutation_neighborhood)
