@@ -606,6 +606,64 @@ typedef struct {
 } pbccs_poa_stats;
 int pbccs_poa_stats_get(pbccs_engine* eng, pbccs_poa_stats* out, int reset);
 
+/* ---- Pairwise alignment (ConsensusCore/src/C++/Align/) ----------------------------------------------
+ * Align (PairwiseAlignment.cpp:125-212: Needleman-Wunsch, int32, GLOBAL only), AlignAffine and
+ * AlignAffineIupac (AffineAlignment.cpp:110-252: two-state affine, float32) for n independent pairs per call,
+ * bit-exact: scores, ties and the traceback come out as the reference's.  The DP runs on the device
+ * (k_align_fill, one move byte per cell and no score matrix in memory; k_align_trace).  AlignLinear is not
+ * provided. */
+#define PBCCS_ALIGN_NW 0
+#define PBCCS_ALIGN_AFFINE 1
+#define PBCCS_ALIGN_AFFINE_IUPAC 2
+
+/* kind PBCCS_ALIGN_NW reads mode (PBCCS_POA_GLOBAL only: any other is the reference's UnsupportedFeatureError)
+ * and the four ints (AlignParams: Match, Mismatch, Insert, Delete; AlignConfig.cpp's default 0, -1, -1, -1);
+ * the affine kinds read the five floats (AffineAlignmentParams; defaults 0, -1, -1, -0.5 and PartialMatchScore
+ * 0, IUPAC-aware -0.25). */
+typedef struct {
+    int kind, mode;
+    int match, mismatch, insert, delete_;
+    float match_score, mismatch_score, gap_open, gap_extend, partial_match_score;
+} pbccs_align_params;
+
+typedef struct {
+    const char* target;   /* columns (j) */
+    int target_len;
+    const char* query;    /* rows (i) */
+    int query_len;
+} pbccs_align_pair;
+
+typedef struct {
+    char* transcript;   /* caller buffer of cap bytes (not NUL-terminated): M R I D, Gusfield's transcript */
+    int cap;
+    int len;            /* transcript length, never more than target_len + query_len */
+    int score_i;        /* NW: Score(I, J) */
+    float score_f;      /* affine: max(M, GAP)(I, J) */
+    int status;         /* PBCCS_OK, or this pair's PBCCS_EINVAL / PBCCS_EOOM / PBCCS_ERANGE */
+} pbccs_align_result;
+
+/* Results in input order.  An empty target gives all I, an empty query all D (no launch).  PBCCS_EINVAL before
+ * any device work: a mode other than GLOBAL, non-finite affine parameters, a negative length, a null sequence
+ * with a positive length; per pair (status) and for the call: an NW pair whose (I + J) * max|param| does not fit
+ * in int32, or a traceback that would leave the matrix (the reference reads outside its matrices there; only
+ * with pathological parameters).  The pairs are split into launches whose move stores fit the align workspace
+ * budget (PBCCS_ALIGN_WORKSPACE_MB, default 2048); a pair that alone exceeds it gets PBCCS_EOOM, as does the
+ * call, with no device work for that pair.  A transcript longer than its buffer sets len and makes the call
+ * return PBCCS_ERANGE after all outputs are written.  The call returns the first failing pair's status
+ * (PBCCS_ERANGE last). */
+int pbccs_align_batch(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_pair* pairs, int n,
+                      pbccs_align_result* out);
+
+/* Align work since the last reset: pairs given, DP cells filled, k_align_fill launches, transcript characters
+ * walked; fill / trace device ms (profiling on); bytes = move-store bytes the launches covered; groups = the
+ * launch groups the workspace budget split the batches into. */
+typedef struct {
+    long long pairs, cells, launches, trace_steps;
+    double fill_ms, trace_ms, bytes;
+    long long groups;
+} pbccs_align_stats;
+int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

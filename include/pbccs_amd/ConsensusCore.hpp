@@ -29,6 +29,11 @@ public:
     explicit InvalidInputError(const std::string& m = "invalid input") : std::runtime_error(m) {}
 };
 
+class UnsupportedFeatureError : public std::runtime_error {
+public:
+    explicit UnsupportedFeatureError(const std::string& m = "unsupported feature") : std::runtime_error(m) {}
+};
+
 class DeviceError : public std::runtime_error {
 public:
     explicit DeviceError(const std::string& m) : std::runtime_error(m) {}

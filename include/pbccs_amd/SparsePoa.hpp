@@ -16,11 +16,10 @@
 #include <string>
 #include <vector>
 
+#include "AlignMode.hpp"
 #include "ConsensusCore.hpp"
 
 namespace ConsensusCore {
-
-enum AlignMode { GLOBAL = PBCCS_POA_GLOBAL, SEMIGLOBAL = PBCCS_POA_SEMIGLOBAL, LOCAL = PBCCS_POA_LOCAL };
 
 // The consensus of a POA; Graph / Path stay inside the engine (ToGraphViz on the SparsePoa gives the dump).
 struct PoaConsensus {

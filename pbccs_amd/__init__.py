@@ -307,6 +307,9 @@ from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E4
                      RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator, RefineRepeats,
                      RefineDinucleotideRepeats)
 from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
+from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
+                    AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
+                    TargetToQueryPositions, UnsupportedFeatureError, align_batch, align_stats)
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -1,0 +1,306 @@
+"""Pairwise alignment on the GPU: the Python mirror of ConsensusCore's Align/ (PairwiseAlignment.hpp,
+AffineAlignment.hpp, AlignConfig.hpp) over the C ABI's pbccs_align_batch.
+
+Align (Needleman-Wunsch, int32), AlignAffine and AlignAffineIupac (two-state affine, float32) run in HIP
+(k_align_fill / k_align_trace), bit-exact with the reference: ties and the traceback come out the same.
+PairwiseAlignment, FromTranscript and TargetToQueryPositions are host-side value code.  There is no CPU
+fallback for the aligners: without the library or a GPU they raise.  AlignLinear is not provided."""
+import ctypes
+import math
+
+from . import lib as _L
+from .lib import load
+
+GLOBAL, SEMIGLOBAL, LOCAL = 0, 1, 2
+NW, AFFINE, AFFINE_IUPAC = 0, 1, 2
+
+
+class InvalidInputError(ValueError):
+    """ConsensusCore::InvalidInputError"""
+
+
+class UnsupportedFeatureError(NotImplementedError):
+    """ConsensusCore::UnsupportedFeatureError"""
+
+
+class AlignParams:
+    """AlignConfig.hpp: AlignParams(Match, Mismatch, Insert, Delete); Default() is edit distance."""
+
+    def __init__(self, match=0, mismatch=-1, insert=-1, delete=-1):
+        self.Match, self.Mismatch, self.Insert, self.Delete = int(match), int(mismatch), int(insert), int(delete)
+
+    @staticmethod
+    def Default():
+        return AlignParams(0, -1, -1, -1)
+
+
+class AlignConfig:
+    def __init__(self, params=None, mode=GLOBAL):
+        self.Params = params if params is not None else AlignParams.Default()
+        self.Mode = mode
+
+    @staticmethod
+    def Default():
+        return AlignConfig(AlignParams.Default(), GLOBAL)
+
+
+class AffineAlignmentParams:
+    def __init__(self, match_score, mismatch_score, gap_open, gap_extend, partial_match_score=0.0):
+        self.MatchScore = float(match_score)
+        self.MismatchScore = float(mismatch_score)
+        self.GapOpen = float(gap_open)
+        self.GapExtend = float(gap_extend)
+        self.PartialMatchScore = float(partial_match_score)
+
+    def _values(self):
+        return (self.MatchScore, self.MismatchScore, self.GapOpen, self.GapExtend, self.PartialMatchScore)
+
+
+def DefaultAffineAlignmentParams():
+    return AffineAlignmentParams(0, -1.0, -1.0, -0.5, 0)
+
+
+def IupacAwareAffineAlignmentParams():
+    return AffineAlignmentParams(0, -1.0, -1.0, -0.5, -0.25)
+
+
+class PairwiseAlignment:
+    """ConsensusCore::PairwiseAlignment (PairwiseAlignment.cpp:51-123): gapped target and query of equal length and
+    Gusfield's transcript (M match, R mismatch, I target gap, D query gap)."""
+
+    def __init__(self, target, query):
+        if len(target) != len(query):
+            raise InvalidInputError("target and query differ in length")
+        tr = []
+        for t, q in zip(target, query):
+            if t == "-" and q == "-":
+                raise InvalidInputError("gap aligned to gap")
+            tr.append("M" if t == q else "I" if t == "-" else "D" if q == "-" else "R")
+        self._target, self._query, self._transcript = target, query, "".join(tr)
+
+    def Target(self):
+        return self._target
+
+    def Query(self):
+        return self._query
+
+    def Transcript(self):
+        return self._transcript
+
+    def Length(self):
+        return len(self._target)
+
+    def Matches(self):
+        return self._transcript.count("M")
+
+    def Errors(self):
+        return self.Length() - self.Matches()
+
+    def Mismatches(self):
+        return self._transcript.count("R")
+
+    def Insertions(self):
+        return self._transcript.count("I")
+
+    def Deletions(self):
+        return self._transcript.count("D")
+
+    def Accuracy(self):
+        return self.Matches() / self.Length() if self.Length() else float("nan")
+
+    @staticmethod
+    def FromTranscript(transcript, unaln_target, unaln_query):
+        """The alignment the transcript spells over the two sequences, or None where it does not map the target
+        onto the query (PairwiseAlignment.cpp:309-368)."""
+        t_len, q_len = len(unaln_target), len(unaln_query)
+        tp = qp = 0
+        at, aq = [], []
+        for x in transcript:
+            if tp > t_len or qp > q_len:
+                return None
+            t = unaln_target[tp] if tp < t_len else "\0"
+            q = unaln_query[qp] if qp < q_len else "\0"
+            if x == "M" or x == "R":
+                if (t == q) != (x == "M"):
+                    return None
+                at.append(t)
+                aq.append(q)
+                tp += 1
+                qp += 1
+            elif x == "I":
+                at.append("-")
+                aq.append(q)
+                qp += 1
+            elif x == "D":
+                at.append(t)
+                aq.append("-")
+                tp += 1
+            else:
+                return None
+        if tp != t_len or qp != q_len:
+            return None
+        return PairwiseAlignment("".join(at), "".join(aq))
+
+    def __repr__(self):
+        return f"PairwiseAlignment({self._target!r}, {self._query!r})"
+
+    def __eq__(self, o):
+        return isinstance(o, PairwiseAlignment) and (self._target, self._query) == (o._target, o._query)
+
+    def __hash__(self):
+        return hash((self._target, self._query))
+
+
+def TargetToQueryPositions(transcript):
+    """For each target position (and one past the end) the query position the alignment maps it to
+    (PairwiseAlignment.cpp:264-303).  Takes a transcript string or a PairwiseAlignment."""
+    if isinstance(transcript, PairwiseAlignment):
+        transcript = transcript.Transcript()
+    ntp = []
+    qp = 0
+    for c in transcript:
+        if c == "M" or c == "R":
+            ntp.append(qp)
+            qp += 1
+        elif c == "D":
+            ntp.append(qp)
+        elif c == "I":
+            qp += 1
+        else:
+            raise InvalidInputError(f"not a transcript character: {c!r}")
+    ntp.append(qp)
+    return ntp
+
+
+def _c_params(kind, params):
+    """Validates on the host (before any engine is touched) and returns the C struct."""
+    c = _L.CAlignParams()
+    c.kind = kind
+    c.mode = GLOBAL
+    if kind == NW:
+        cfg = params if params is not None else AlignConfig.Default()
+        if isinstance(cfg, AlignParams):
+            cfg = AlignConfig(cfg, GLOBAL)
+        if cfg.Mode != GLOBAL:
+            raise UnsupportedFeatureError("Only GLOBAL alignment supported at present")
+        c.mode = cfg.Mode
+        c.match, c.mismatch, c.insert, c.delete_ = (cfg.Params.Match, cfg.Params.Mismatch, cfg.Params.Insert,
+                                                      cfg.Params.Delete)
+    elif kind in (AFFINE, AFFINE_IUPAC):
+        if params is None:
+            params = DefaultAffineAlignmentParams() if kind == AFFINE else IupacAwareAffineAlignmentParams()
+        vals = params._values()
+        if not all(math.isfinite(v) for v in vals):
+            raise InvalidInputError("affine alignment parameters must be finite")
+        c.match_score, c.mismatch_score, c.gap_open, c.gap_extend, c.partial_match_score = vals
+    else:
+        raise InvalidInputError(f"unknown alignment kind {kind!r}")
+    return c
+
+
+def _encode(s):
+    return s if isinstance(s, bytes) else s.encode("latin-1")
+
+
+def align_batch_raw(pairs, kind, params=None, engine=None, caps=None):
+    """pbccs_align_batch as it stands: (return code, [(transcript, score, status, len) per pair]).  pairs are
+    (target, query) strings; caps overrides the transcript capacities (default target + query lengths).
+    Marshalling is flat: one blob with pointer tables and one shared transcript buffer."""
+    import numpy as np
+    from .quiver import _struct_dtype
+    c = _c_params(kind, params)
+    if engine is None:
+        from . import default_engine
+        engine = default_engine()
+    n = len(pairs)
+    enc = [_encode(s) for p in pairs for s in p]
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int64, count=2 * n)
+    blob = ctypes.create_string_buffer(b"".join(enc), max(1, int(lens.sum())))
+    starts = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(lens, out=starts[1:])
+    ptrs = (ctypes.addressof(blob) + starts[:-1]).astype(np.uint64)
+    cap = (lens[0::2] + lens[1::2]) if caps is None else np.asarray(caps, dtype=np.int64)
+    ostart = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(cap, out=ostart[1:])
+    obuf = ctypes.create_string_buffer(max(1, int(ostart[-1])))
+    ins = np.zeros(max(1, n), dtype=_struct_dtype(_L.CAlignPair))
+    outs = np.zeros(max(1, n), dtype=_struct_dtype(_L.CAlignResult))
+    if n:
+        ins["target"][:n] = ptrs[0::2]
+        ins["target_len"][:n] = lens[0::2]
+        ins["query"][:n] = ptrs[1::2]
+        ins["query_len"][:n] = lens[1::2]
+        outs["transcript"][:n] = ctypes.addressof(obuf) + ostart[:-1]
+        outs["cap"][:n] = cap
+    rc = load().pbccs_align_batch(engine._h, ctypes.byref(c), ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CAlignPair)),
+                                  n, ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CAlignResult)))
+    raw = obuf.raw
+    os_, ln, caps_l, st = ostart.tolist(), outs["len"][:n].tolist(), cap.tolist(), outs["status"][:n].tolist()
+    score = outs["score_i"][:n].tolist() if kind == NW else outs["score_f"][:n].tolist()
+    res = []
+    for k in range(n):
+        tr = raw[os_[k]:os_[k] + ln[k]].decode("latin-1") if st[k] == 0 and ln[k] <= caps_l[k] else None
+        res.append((tr, score[k], st[k], ln[k]))
+    return rc, res
+
+
+def _from_device_transcript(tr, target, query):
+    """FromTranscript for the batch path, column-wise in numpy instead of a per-character Python loop.  The same
+    refusals: None unless the transcript maps the target onto the query."""
+    import numpy as np
+    x = np.frombuffer(tr.encode("latin-1"), dtype=np.uint8)
+    t = np.frombuffer(_encode(target), dtype=np.uint8)
+    q = np.frombuffer(_encode(query), dtype=np.uint8)
+    on_t, on_q = x != ord("I"), x != ord("D")
+    if int(on_t.sum()) != len(t) or int(on_q.sum()) != len(q) or not np.isin(x, np.frombuffer(b"MRID", np.uint8)).all():
+        return None
+    at = np.full(len(x), ord("-"), dtype=np.uint8)
+    aq = np.full(len(x), ord("-"), dtype=np.uint8)
+    at[on_t] = t
+    aq[on_q] = q
+    both = on_t & on_q
+    if not ((at == aq)[both] == (x == ord("M"))[both]).all():
+        return None
+    a = PairwiseAlignment.__new__(PairwiseAlignment)
+    a._target, a._query, a._transcript = at.tobytes().decode("latin-1"), aq.tobytes().decode("latin-1"), tr
+    return a
+
+
+def align_batch(pairs, kind, params=None, engine=None):
+    """Aligns many (target, query) pairs in one call.  kind: NW (params: AlignConfig), AFFINE or AFFINE_IUPAC
+    (params: AffineAlignmentParams).  Returns ([PairwiseAlignment], [score]) in input order; the score is
+    Score(I, J) (int) for NW and max(M, GAP)(I, J) (float32 value) for the affine kinds."""
+    rc, res = align_batch_raw(pairs, kind, params, engine)
+    _L.check(rc)
+    alns = []
+    for (t, q), (tr, _, _, _) in zip(pairs, res):
+        a = _from_device_transcript(tr, t, q)
+        if a is None:
+            raise _L.PbccsError(-3, "the device returned a transcript that does not map the target onto the query")
+        alns.append(a)
+    return alns, [r[1] for r in res]
+
+
+def Align(target, query, config=None, return_score=False, engine=None):
+    """PairwiseAlignment* Align(target, query, int* score, AlignConfig) (PairwiseAlignment.cpp:125-212)."""
+    alns, scores = align_batch([(target, query)], NW, config, engine)
+    return (alns[0], scores[0]) if return_score else alns[0]
+
+
+def AlignAffine(target, query, params=None, engine=None):
+    """AlignAffine(target, query, AffineAlignmentParams = DefaultAffineAlignmentParams())."""
+    return align_batch([(target, query)], AFFINE, params, engine)[0][0]
+
+
+def AlignAffineIupac(target, query, params=None, engine=None):
+    """AlignAffineIupac(target, query, AffineAlignmentParams = IupacAwareAffineAlignmentParams())."""
+    return align_batch([(target, query)], AFFINE_IUPAC, params, engine)[0][0]
+
+
+def align_stats(engine=None, reset=False):
+    if engine is None:
+        from . import default_engine
+        engine = default_engine()
+    s = _L.CAlignStats()
+    _L.check(load().pbccs_align_stats_get(engine._h, ctypes.byref(s), 1 if reset else 0))
+    return {k: getattr(s, k) for k, _ in _L.CAlignStats._fields_}

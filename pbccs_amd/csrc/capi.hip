@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "align_kernels.hpp"
 #include "engine.hpp"
 #include "driver.hpp"
 #include "poa_engine.hpp"
@@ -85,6 +86,16 @@ struct pbccs_engine {
     // pools are allocated once; calls on one engine take turns on it
     std::unique_ptr<quiver::QuiverBatch> quiverBatch;
     std::mutex quiverMu;
+    // the pairwise aligner's workspace (made on first use): its own stream and move store, apart from the polish
+    // slots and the POA pools; calls on one engine take turns on it
+    std::unique_ptr<align::AlignRunner> align;
+    std::mutex alignMu;
+    align::AlignRunner& Align()
+    {
+        if (!align) align.reset(new align::AlignRunner(device));
+        align->profiling = profiling;
+        return *align;
+    }
     Workspace* Slot(int s)
     {
         while ((int)slots.size() <= s) slots.emplace_back(new Workspace(true));
@@ -2101,6 +2112,76 @@ int pbccs_poa_stats_get(pbccs_engine* eng, pbccs_poa_stats* out, int reset)
         }
         *out = pbccs_poa_stats{s.alignments, s.cells,  s.launches, s.traceSteps, s.fillMs,     s.traceMs,
                                s.bytes,      s.progMs, s.deviceMs, s.threadMs,  s.consensusMs, s.totalMs};
+        return PBCCS_OK;
+    });
+}
+
+// ---- pairwise alignment (align_kernels.hpp) --------------------------------------------------------------
+int pbccs_align_batch(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_pair* pairs, int n,
+                      pbccs_align_result* out)
+{
+    if (!eng || !params || n < 0 || (n > 0 && (!pairs || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    const pbccs_align_params& a = *params;
+    if (a.kind != PBCCS_ALIGN_NW && a.kind != PBCCS_ALIGN_AFFINE && a.kind != PBCCS_ALIGN_AFFINE_IUPAC)
+        return fail(PBCCS_EINVAL, "unknown alignment kind");
+    if (a.kind == PBCCS_ALIGN_NW && a.mode != PBCCS_POA_GLOBAL)
+        return fail(PBCCS_EINVAL, "Only GLOBAL alignment supported at present");
+    if (a.kind != PBCCS_ALIGN_NW &&
+        !(std::isfinite(a.match_score) && std::isfinite(a.mismatch_score) && std::isfinite(a.gap_open) &&
+          std::isfinite(a.gap_extend) && std::isfinite(a.partial_match_score)))
+        return fail(PBCCS_EINVAL, "affine alignment parameters must be finite");
+    for (int k = 0; k < n; ++k) {
+        const pbccs_align_pair& p = pairs[k];
+        if (p.target_len < 0 || p.query_len < 0 || (p.target_len > 0 && !p.target) || (p.query_len > 0 && !p.query))
+            return fail(PBCCS_EINVAL, "bad pbccs_align_pair");
+        if (out[k].cap < 0 || (out[k].cap > 0 && !out[k].transcript)) return fail(PBCCS_EINVAL, "bad pbccs_align_result");
+    }
+    return guarded([&] {
+        const align::AlignScoring sc{a.kind,        a.match,          a.mismatch, a.insert,     a.delete_,
+                                     a.match_score, a.mismatch_score, a.gap_open, a.gap_extend, a.partial_match_score};
+        std::vector<align::PairView> pv(n);
+        for (int k = 0; k < n; ++k) pv[k] = align::PairView{pairs[k].target, pairs[k].target_len, pairs[k].query, pairs[k].query_len};
+        std::vector<align::PairResult> res(n);
+        {
+            std::lock_guard<std::mutex> lk(eng->alignMu);
+            eng->Align().Run(sc, pv.data(), n, res.data());
+        }
+        int rc = PBCCS_OK;
+        bool small = false;
+        for (int k = 0; k < n; ++k) {
+            pbccs_align_result& o = out[k];
+            const align::PairResult& r = res[k];
+            o.len = (int)r.transcript.size();
+            o.score_i = r.scoreI;
+            o.score_f = r.scoreF;
+            o.status = r.status;
+            if (r.status != PBCCS_OK) {
+                if (rc == PBCCS_OK) rc = r.status;
+                continue;
+            }
+            if (o.len > o.cap) {
+                o.status = PBCCS_ERANGE;
+                small = true;
+                continue;
+            }
+            if (o.len > 0) std::memcpy(o.transcript, r.transcript.data(), (size_t)o.len);
+        }
+        if (rc == PBCCS_EINVAL) return fail(rc, "a pair cannot be aligned (int32 overflow, or a traceback that leaves the matrix)");
+        if (rc == PBCCS_EOOM) return fail(rc, "a pair's move store exceeds the align workspace (PBCCS_ALIGN_WORKSPACE_MB)");
+        if (rc != PBCCS_OK) return fail(rc, "alignment failed");
+        if (small) return fail(PBCCS_ERANGE, "transcript buffer too small");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->alignMu);
+        const align::AlignStats s = eng->align ? eng->align->stats : align::AlignStats();
+        *out = pbccs_align_stats{s.pairs, s.cells, s.launches, s.traceSteps, s.fillMs, s.traceMs, s.bytes, s.groups};
+        if (reset && eng->align) eng->align->stats = align::AlignStats();
         return PBCCS_OK;
     });
 }

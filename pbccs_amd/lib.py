@@ -160,6 +160,29 @@ class CDiploidStats(ctypes.Structure):
                 ("sites_reported", ctypes.c_longlong)]
 
 
+class CAlignParams(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("mode", ctypes.c_int), ("match", ctypes.c_int), ("mismatch", ctypes.c_int),
+                ("insert", ctypes.c_int), ("delete_", ctypes.c_int), ("match_score", ctypes.c_float),
+                ("mismatch_score", ctypes.c_float), ("gap_open", ctypes.c_float), ("gap_extend", ctypes.c_float),
+                ("partial_match_score", ctypes.c_float)]
+
+
+class CAlignPair(ctypes.Structure):
+    _fields_ = [("target", ctypes.c_char_p), ("target_len", ctypes.c_int), ("query", ctypes.c_char_p),
+                ("query_len", ctypes.c_int)]
+
+
+class CAlignResult(ctypes.Structure):
+    _fields_ = [("transcript", ctypes.c_char_p), ("cap", ctypes.c_int), ("len", ctypes.c_int),
+                ("score_i", ctypes.c_int), ("score_f", ctypes.c_float), ("status", ctypes.c_int)]
+
+
+class CAlignStats(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_longlong), ("cells", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("trace_steps", ctypes.c_longlong), ("fill_ms", ctypes.c_double), ("trace_ms", ctypes.c_double),
+                ("bytes", ctypes.c_double), ("groups", ctypes.c_longlong)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -261,6 +284,10 @@ SIGNATURES = {
     "pbccs_poa_consensus": (I, [P, ctypes.POINTER(ctypes.c_char_p), PI, I, I, I, ctypes.c_char_p, I, PI, I,
                                 ctypes.c_char_p, I, PI]),
     "pbccs_poa_stats_get": (I, [P, ctypes.POINTER(CPoaStats), I]),
+    # pairwise alignment
+    "pbccs_align_batch": (I, [P, ctypes.POINTER(CAlignParams), ctypes.POINTER(CAlignPair), I,
+                              ctypes.POINTER(CAlignResult)]),
+    "pbccs_align_stats_get": (I, [P, ctypes.POINTER(CAlignStats), I]),
     "pbccs_ccs_batch": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.c_longlong, ctypes.POINTER(CPolishOptions),
                             ctypes.POINTER(CCcsOutput)]),
 }
