@@ -664,6 +664,63 @@ typedef struct {
 } pbccs_align_stats;
 int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset);
 
+/* ---- MapToDraft: placing reads on a finished draft ---------------------------------------------------
+ * What SparsePoa::OrientAndAddRead(read, minScoreToAdd) followed by FindConsensus reports for a read on a graph
+ * that holds only the draft as one unbranched path: a LOCAL alignment of the read, as given and reverse
+ * complemented, against the linear draft with DefaultPoaConfig's scores (match 3, mismatch -5, insert -4,
+ * delete -4), ties as the reference's (candidates Start, diagonal, Delete, Extra, a later one only when strictly
+ * greater; the end cell is the smallest draft column, then the smallest read row, holding the maximum).  The DP
+ * runs on the device (k_map_fill): every cell carries its start cell, no matrix, move or path reaches memory.
+ * The reference has no such call (Consensus.h:102-103 leaves it a TODO); it is what lets a POA capped by
+ * max_poa_coverage keep the reads past the cap (pbccs_ccs_batch_ex). */
+typedef struct {
+    const char* draft;
+    int draft_len;
+    const char* const* seqs;   /* n_reads reads; a NULL or zero-length read is never mapped */
+    const int* lens;
+    int n_reads;
+} pbccs_map_input;
+
+typedef struct {
+    int* mapped;    /* n_reads: 1 mapped, 0 not (both orientations below min_score_to_add, or no read) */
+    int* rc;        /* n_reads: PoaAlignmentSummary::ReverseComplementedRead */
+    int* extents;   /* 4 * n_reads: ExtentOnRead begin/end (in the reverse complement's coordinates when rc),
+                       ExtentOnConsensus begin/end; a best score of 0 gives 0 0 0 0 */
+    int* score;     /* n_reads: the chosen orientation's score (the larger of the two when not mapped) */
+} pbccs_map_output;
+
+/* Orientation as SparsePoa.cpp:112-132: forward if c1 >= c2 && c1 >= min_score_to_add, else reverse if c2 >= c1
+ * && c2 >= min_score_to_add, else not mapped.  Any output array may be NULL.  PBCCS_EINVAL before any device
+ * work: an empty or NULL draft, a negative length, a NULL read with a positive length, a draft or read longer
+ * than 65535 (a start cell is packed in 32 bits).  Reads taller than one strip of rows hand their boundary row
+ * through a per-job buffer; the batch is split into launches whose buffers fit PBCCS_MAP_WORKSPACE_KB (default
+ * 262144), and a read whose own buffers exceed it is left unmapped and makes the call return PBCCS_EOOM after
+ * every other read was mapped, with no device work for that read. */
+int pbccs_map_batch(pbccs_engine* eng, const pbccs_map_input* in, int n, float min_score_to_add,
+                    pbccs_map_output* out);
+
+/* Mapping work since the last reset: reads given, DP cells (2 (I + 1) J per read that reached the device),
+ * k_map_fill launches, row strips run, device ms (profiling on). */
+typedef struct {
+    long long jobs, cells, launches, strips;
+    double device_ms;
+} pbccs_map_stats;
+int pbccs_map_stats_get(pbccs_engine* eng, pbccs_map_stats* out, int reset);
+
+/* pbccs_ccs_batch with options.  map_past_cap != 0: once max_poa_coverage reads were added and the draft taken
+ * exactly as without it, every later read of FilterReads' order is placed on the draft with pbccs_map_batch's
+ * aligner (min_score_to_add 0) and goes through ExtractMappedRead like a POA read; a read FilterReads dropped or
+ * the mapping refused is a placeholder that counts in the drop fraction's denominator, as a read the POA
+ * rejected does.  AddRead order stays FilterReads' order.  map_past_cap == 0, or a cap no read lies past, is
+ * pbccs_ccs_batch. */
+typedef struct {
+    long long max_poa_coverage;   /* >= 1 */
+    int map_past_cap;
+} pbccs_ccs_options;
+void pbccs_ccs_options_default(pbccs_ccs_options* o);   /* no cap, map_past_cap 0 */
+int pbccs_ccs_batch_ex(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                       const pbccs_polish_options* opts, pbccs_ccs_output* out);
+
 #ifdef __cplusplus
 }
 #endif

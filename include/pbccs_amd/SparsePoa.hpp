@@ -8,6 +8,7 @@
 //   PacBio::CCS::PoaAlignmentSummary / PoaAlignmentOptions include/pacbio/ccs/SparsePoa.h:57-85
 //   PacBio::CCS::SparsePoa                                 include/pacbio/ccs/SparsePoa.h:87-131
 //   ConsensusCore::PoaConsensus::FindConsensus             ConsensusCore/include/ConsensusCore/Poa/PoaConsensus.hpp:60-97
+// Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch).
 #pragma once
 
 #include <climits>
@@ -140,6 +141,38 @@ private:
     int reads_ = 0;
     size_t bases_ = 0;
 };
+
+// MapToDraft(draft, reads, minScoreToAdd): what OrientAndAddRead + FindConsensus would report for each read on a
+// SparsePoa that holds only the draft -- orientation and the two extents, plus AlignmentScore -- from one
+// pbccs_map_batch call (no graph).  The reference leaves this a TODO (include/pacbio/ccs/Consensus.h:102-103).
+// mapped (optional) receives one flag per read: false where OrientAndAddRead would have returned -1 (both
+// orientations below minScoreToAdd, or an empty read); that read's summary is default-constructed.
+inline std::vector<PoaAlignmentSummary> MapToDraft(const std::string& draft, const std::vector<std::string>& reads,
+                                                   float minScoreToAdd = 0, std::vector<bool>* mapped = nullptr)
+{
+    const int n = (int)reads.size();
+    std::vector<const char*> p;
+    std::vector<int> len;
+    for (const std::string& r : reads) {
+        p.push_back(r.data());
+        len.push_back((int)r.size());
+    }
+    std::vector<int> ok(n + 1), rc(n + 1), ext(4 * n + 4), score(n + 1);
+    const pbccs_map_input in{draft.data(), (int)draft.size(), p.data(), len.data(), n};
+    pbccs_map_output out{ok.data(), rc.data(), ext.data(), score.data()};
+    ConsensusCore::detail::Check(pbccs_map_batch(ConsensusCore::detail::DefaultEngine(), &in, 1, minScoreToAdd, &out));
+    std::vector<PoaAlignmentSummary> summaries(n);
+    if (mapped) mapped->assign(n, false);
+    for (int k = 0; k < n; ++k) {
+        if (!ok[k]) continue;
+        if (mapped) (*mapped)[k] = true;
+        summaries[k].ReverseComplementedRead = rc[k] != 0;
+        summaries[k].ExtentOnRead = Interval(ext[4 * k], ext[4 * k + 1]);
+        summaries[k].ExtentOnConsensus = Interval(ext[4 * k + 2], ext[4 * k + 3]);
+        summaries[k].AlignmentScore = (float)score[k];
+    }
+    return summaries;
+}
 
 }  // namespace CCS
 }  // namespace PacBio

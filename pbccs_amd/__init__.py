@@ -310,6 +310,7 @@ from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
 from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
                     TargetToQueryPositions, UnsupportedFeatureError, align_batch, align_stats)
+from .mapping import map_batch, map_stats, map_to_draft  # noqa: E402,F401
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -25,6 +25,7 @@
 #include "align_kernels.hpp"
 #include "engine.hpp"
 #include "driver.hpp"
+#include "map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
 
@@ -95,6 +96,15 @@ struct pbccs_engine {
         if (!align) align.reset(new align::AlignRunner(device));
         align->profiling = profiling;
         return *align;
+    }
+    // the draft mapper's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<map::MapRunner> mapper;
+    std::mutex mapMu;
+    map::MapRunner& Map()
+    {
+        if (!mapper) mapper.reset(new map::MapRunner(device));
+        mapper->profiling = profiling;
+        return *mapper;
     }
     Workspace* Slot(int s)
     {
@@ -2186,6 +2196,60 @@ int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset)
     });
 }
 
+// ---- MapToDraft (map_kernels.hpp) ---------------------------------------------------------------------------
+int pbccs_map_batch(pbccs_engine* eng, const pbccs_map_input* in, int n, float min_score_to_add,
+                    pbccs_map_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    for (int g = 0; g < n; ++g) {
+        const pbccs_map_input& m = in[g];
+        if (!m.draft || m.draft_len <= 0) return fail(PBCCS_EINVAL, "empty draft");
+        if (m.n_reads < 0 || (m.n_reads > 0 && (!m.seqs || !m.lens))) return fail(PBCCS_EINVAL, "bad pbccs_map_input");
+        if (m.draft_len > map::kMaxLen) return fail(PBCCS_EINVAL, "draft longer than 65535");
+        for (int r = 0; r < m.n_reads; ++r) {
+            if (m.lens[r] < 0 || (m.lens[r] > 0 && !m.seqs[r]))
+                return fail(PBCCS_EINVAL, "bad read (NULL sequence or negative length)");
+            if (m.lens[r] > map::kMaxLen) return fail(PBCCS_EINVAL, "read longer than 65535");
+        }
+    }
+    return guarded([&] {
+        std::vector<map::MapGroup> groups(n);
+        for (int g = 0; g < n; ++g)
+            groups[g] = map::MapGroup{in[g].draft, in[g].draft_len, in[g].seqs, in[g].lens, in[g].n_reads};
+        std::vector<map::MapResult> res;
+        {
+            std::lock_guard<std::mutex> lk(eng->mapMu);
+            eng->Map().Run(groups.data(), n, min_score_to_add, &res);
+        }
+        bool oom = false;
+        size_t k = 0;
+        for (int g = 0; g < n; ++g)
+            for (int r = 0; r < in[g].n_reads; ++r, ++k) {
+                const map::MapResult& m = res[k];
+                oom = oom || m.status == PBCCS_EOOM;
+                if (out[g].mapped) out[g].mapped[r] = m.mapped;
+                if (out[g].rc) out[g].rc[r] = m.rc;
+                if (out[g].score) out[g].score[r] = m.score;
+                if (out[g].extents)
+                    for (int e = 0; e < 4; ++e) out[g].extents[4 * r + e] = m.ext[e];
+            }
+        if (oom) return fail(PBCCS_EOOM, "a read's boundary buffers exceed the map workspace (PBCCS_MAP_WORKSPACE_KB)");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_map_stats_get(pbccs_engine* eng, pbccs_map_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->mapMu);
+        const map::MapStats s = eng->mapper ? eng->mapper->stats : map::MapStats();
+        *out = pbccs_map_stats{s.jobs, s.cells, s.launches, s.strips, s.deviceMs};
+        if (reset && eng->mapper) eng->mapper->stats = map::MapStats();
+        return PBCCS_OK;
+    });
+}
+
 // One POA chunk of the pipelined ccs batch: its live ZMWs and everything their polish inputs point into.
 struct CcsChunk {
     std::vector<int> zs;   // caller indices of the chunk's ZMWs
@@ -2215,9 +2279,12 @@ static void bind_polish_outputs(CcsChunk* C, const pbccs_ccs_output* out)
 }
 
 // The POA draft of one chunk (Consensus.h:422-425, 352-390), then TooShort and ExtractMappedRead
-// (Consensus.h:427-471) into the chunk's polish inputs.
+// (Consensus.h:427-471) into the chunk's polish inputs.  mapPastCap: the reads the maxPoaCov stop never reached
+// (key -2) are placed on the finished drafts and treated like POA reads: one MapRunner call per POA slice, on the
+// slice's thread once its drafts are final, while the other slices' POA rounds go on.
 static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const pbccs_polish_options& o,
-                            long long max_poa_coverage, const std::vector<std::vector<driver::Subread>>& sub,
+                            long long max_poa_coverage, bool mapPastCap,
+                            const std::vector<std::vector<driver::Subread>>& sub,
                             const std::vector<std::vector<int>>& order, pbccs_ccs_output* out, CcsChunk* C)
 {
     const size_t m = C->zs.size();
@@ -2226,7 +2293,45 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
         for (int k : order[C->zs[q]]) poaReads[q].push_back(k >= 0 ? &sub[C->zs[q]][k].seq : nullptr);
     std::vector<std::vector<int>> keys, ext;
     std::vector<std::vector<char>> rc;
-    poa::PoaBatch(eng->PoaRunners(), poaReads, max_poa_coverage, -1, &C->css, &keys, &rc, &ext);
+    // past the cap: mapRes[q] holds one result per read of ZMW q past the stop, in FilterReads order
+    std::vector<std::vector<map::MapResult>> mapRes(m);
+    const std::function<void(int, int)> mapSlice = [&](int q0, int q1) {
+        std::vector<map::MapGroup> groups;
+        std::vector<size_t> groupQ;
+        std::vector<std::vector<const char*>> ptrs(q1 - q0);
+        std::vector<std::vector<int>> lens(q1 - q0);
+        for (int q = q0; q < q1; ++q) {
+            std::vector<const char*>& pq = ptrs[q - q0];
+            std::vector<int>& lq = lens[q - q0];
+            const int z = C->zs[q];
+            if ((int)C->css[q].size() < o.min_length || C->css[q].empty()) continue;
+            for (size_t i = 0; i < keys[q].size(); ++i) {
+                if (keys[q][i] != -2) continue;
+                const int k = order[z][i];
+                pq.push_back(k >= 0 ? sub[z][k].seq.data() : nullptr);
+                lq.push_back(k >= 0 ? (int)sub[z][k].seq.size() : 0);
+            }
+            if (pq.empty()) continue;
+            if ((int)C->css[q].size() > map::kMaxLen) throw std::invalid_argument("map_past_cap: draft longer than 65535");
+            groups.push_back(map::MapGroup{C->css[q].data(), (int)C->css[q].size(), pq.data(), lq.data(), (int)pq.size()});
+            groupQ.push_back((size_t)q);
+        }
+        if (groups.empty()) return;
+        std::vector<map::MapResult> res;
+        {
+            std::lock_guard<std::mutex> lk(eng->mapMu);   // the slices take turns on the engine's mapper
+            eng->Map().Run(groups.data(), (int)groups.size(), 0.f, &res);
+        }
+        size_t at = 0;
+        for (size_t g = 0; g < groups.size(); ++g) {
+            mapRes[groupQ[g]].assign(res.begin() + at, res.begin() + at + groups[g].n);
+            at += (size_t)groups[g].n;
+        }
+        for (const map::MapResult& r : res)
+            if (r.status != PBCCS_OK) throw DeviceOom("a read's boundary buffers exceed the map workspace");
+    };
+    poa::PoaBatch(eng->PoaRunners(), poaReads, max_poa_coverage, -1, &C->css, &keys, &rc, &ext,
+                  mapPastCap ? &mapSlice : nullptr);
     C->mapped.resize(m);
     C->seqPtr.resize(m);
     C->lens.resize(m);
@@ -2248,13 +2353,21 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
         }
         std::vector<unsigned char> added;
         const std::vector<int>& kk = keys[q];
-        for (size_t i = 0; i < kk.size() && kk[i] != -2; ++i) {
+        size_t past = 0;
+        for (size_t i = 0; i < kk.size() && (kk[i] != -2 || mapPastCap); ++i) {
             driver::MappedRead mr;
             const int key = kk[i];
-            const bool ok = key >= 0 &&
-                            driver::ExtractMappedRead(sub[z][order[z][i]], rc[q][key] != 0, ext[q][4 * key],
-                                                      ext[q][4 * key + 1], ext[q][4 * key + 2], ext[q][4 * key + 3],
-                                                      (size_t)o.min_length, &mr);
+            bool ok;
+            if (key == -2) {
+                const map::MapResult& r = mapRes[q][past++];
+                ok = r.mapped && driver::ExtractMappedRead(sub[z][order[z][i]], r.rc != 0, r.ext[0], r.ext[1], r.ext[2],
+                                                           r.ext[3], (size_t)o.min_length, &mr);
+            } else {
+                ok = key >= 0 &&
+                     driver::ExtractMappedRead(sub[z][order[z][i]], rc[q][key] != 0, ext[q][4 * key],
+                                               ext[q][4 * key + 1], ext[q][4 * key + 2], ext[q][4 * key + 3],
+                                               (size_t)o.min_length, &mr);
+            }
             C->mapped[q].push_back(ok ? mr : driver::MappedRead());
             added.push_back(ok ? 1 : 0);
             C->full[q].push_back(ok && sub[z][order[z][i]].FullPass() ? 1 : 0);
@@ -2287,8 +2400,8 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
     bind_polish_outputs(C, out);
 }
 
-int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
-                    const pbccs_polish_options* opts, pbccs_ccs_output* out)
+static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
+                          bool mapPastCap, const pbccs_polish_options* opts, pbccs_ccs_output* out)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
     pbccs_polish_options o;
@@ -2305,6 +2418,8 @@ int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long lo
             for (int r = 0; r < in[z].n_subreads; ++r)
                 if (in[z].lens[r] < 0 || (in[z].lens[r] > 0 && !in[z].seqs[r]))
                     return fail(PBCCS_EINVAL, "bad subread (NULL sequence or negative length)");
+                else if (mapPastCap && in[z].lens[r] > map::kMaxLen)
+                    return fail(PBCCS_EINVAL, "map_past_cap: subread longer than 65535");
         }
         for (int z = 0; z < n; ++z) {   // every per-read slot starts as "not added"
             for (int r = 0; r < in[z].n_subreads; ++r) {
@@ -2447,7 +2562,7 @@ int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long lo
             }
             const double d0 = since();
             try {
-                ccs_draft_chunk(eng, in, o, max_poa_coverage, sub, order, out, &chunks[c]);
+                ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, sub, order, out, &chunks[c]);
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d draft zmws %zu %.1f-%.1f ms\n", c, chunks[c].zs.size(), d0,
                                  since());
@@ -2529,6 +2644,28 @@ int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long lo
         }
         return draftRange ? fail(PBCCS_ERANGE, "draft buffer too small") : PBCCS_OK;
     });
+}
+
+int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
+                    const pbccs_polish_options* opts, pbccs_ccs_output* out)
+{
+    return ccs_batch_impl(eng, in, n, max_poa_coverage, false, opts, out);
+}
+
+void pbccs_ccs_options_default(pbccs_ccs_options* o)
+{
+    if (!o) return;
+    o->max_poa_coverage = std::numeric_limits<long long>::max();
+    o->map_past_cap = 0;
+}
+
+int pbccs_ccs_batch_ex(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                       const pbccs_polish_options* opts, pbccs_ccs_output* out)
+{
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, opts, out);
 }
 
 }  // extern "C"

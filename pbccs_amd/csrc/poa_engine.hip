@@ -931,7 +931,8 @@ void PoaSlice(PoaRunner& R, const std::vector<std::vector<const std::string*>>& 
 
 void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vector<const std::string*>>& reads,
               long long maxCov, int minCov, std::vector<std::string>* consensus, std::vector<std::vector<int>>* keys,
-              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents)
+              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents,
+              const std::function<void(int, int)>* afterSlice)
 {
     const int nz = (int)reads.size();
     consensus->assign(nz, std::string());
@@ -957,6 +958,7 @@ void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vec
             try {
                 PoaSlice(*runners[k], reads, cut[k], std::max(cut[k], cut[k + 1]), maxCov, minCov, consensus, keys, rc,
                          extents);
+                if (afterSlice) (*afterSlice)(cut[k], std::max(cut[k], cut[k + 1]));
             } catch (...) {
                 err[k] = std::current_exception();
             }

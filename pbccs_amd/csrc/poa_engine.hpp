@@ -244,9 +244,12 @@ struct ZmwPoa {
 // taken; keys[z][r] = key, -2 past the coverage stop.  minCov < 0: (cov < 5) ? 1 : (cov + 1) / 2 - 1.
 // The ZMWs are split into one slice per runner (about equal read bases each); the slices run concurrently,
 // so one slice's host work (column programs, threading) overlaps the other's kernels.
+// afterSlice (optional) is called on a slice's thread with its ZMW range [z0, z1) once that slice's outputs are
+// final, while the other slices may still be running.
 void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vector<const std::string*>>& reads,
               long long maxCov, int minCov, std::vector<std::string>* consensus, std::vector<std::vector<int>>* keys,
-              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents);
+              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents,
+              const std::function<void(int, int)>* afterSlice = nullptr);
 
 }  // namespace poa
 }  // namespace pbccs

@@ -106,13 +106,29 @@ def poa_inputs(reads, poa, max_poa_coverage=None):
     return draft, keys, summaries
 
 
-def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None):
+_PLACEHOLDER = {"seq": None, "strand": 0, "ts": 0, "te": 0, "full_pass": False}
+
+
+def _past_cap(rest, summaries, min_length):
+    """The entries of FilterReads' order the maxPoaCov stop never reached, with the summary ({"rc", "read",
+    "tpl"}, or None) the mapping onto the finished draft gave each.  A dropped read (None) and an unmapped one
+    become placeholders, as reads the POA rejected do."""
+    out = []
+    for r, sm in zip(rest, summaries):
+        mr = extract_mapped_read(r, sm, min_length) if r is not None and sm is not None else None
+        out.append(mr if mr is not None else dict(_PLACEHOLDER))
+    return out
+
+
+def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None):
     """One ZMW's subreads -> the polish boundary's ZMW dict, or (status, None) when the ZMW ends before the
     scorer: NoSubreads (Consensus.h:414-420) or TooShort (:427-434).
 
     chunk: {"snr": 4 floats, "reads": [{"seq", "flags"}]}.  Returns (None, zmw) on success, where zmw is
     {"draft", "snr", "reads"} and reads holds one entry per POA key in order: the mapped read, or a
-    placeholder {"seq": None} for a read the POA or ExtractMappedRead skipped."""
+    placeholder {"seq": None} for a read the POA or ExtractMappedRead skipped.
+    mapper (optional, a callable with mapping.map_to_draft's contract): the reads past max_poa_coverage are
+    placed on the draft with it and follow the POA's reads, one entry per read of FilterReads' order."""
     reads = filter_reads(chunk["reads"], min_length)
     if not reads or all(r is None for r in reads):
         return "NoSubreads", None
@@ -123,18 +139,31 @@ def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None):
     for i, key in enumerate(keys):
         mr = extract_mapped_read(reads[i], summaries[key], min_length) if key >= 0 else None
         out.append(mr if mr is not None else {"seq": None, "strand": 0, "ts": 0, "te": 0, "full_pass": False})
+    if mapper is not None:
+        rest = reads[len(keys):]
+        summ = iter(mapper(draft, [r["seq"] for r in rest if r is not None]) if any(r is not None for r in rest) else [])
+        out += _past_cap(rest, [None if r is None else next(summ) for r in rest], min_length)
     return None, {"draft": draft, "snr": list(chunk["snr"]), "reads": out}
 
 
-def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None):
+def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, map_past_cap=False):
     """zmw_input for many ZMWs at once, with the POA of all of them on the GPU in one pbccs_poa_batch
-    (every ZMW adds its next subread in the same device round).  Returns [(status, zmw)] as zmw_input."""
+    (every ZMW adds its next subread in the same device round).  Returns [(status, zmw)] as zmw_input.
+    map_past_cap: the reads past max_poa_coverage of all ZMWs are placed on their drafts in one pbccs_map_batch."""
     from . import poa as _poa
     filtered = [filter_reads(c["reads"], min_length) for c in chunks]
     idx = [z for z, rs in enumerate(filtered) if rs and not all(r is None for r in rs)]
     out = [("NoSubreads", None)] * len(chunks)
     res = _poa.poa_batch([[None if r is None else r["seq"] for r in filtered[z]] for z in idx],
                          max_coverage=max_poa_coverage, engine=engine)
+    past = {}
+    if map_past_cap:
+        from . import mapping as _mapping
+        todo = [(z, r) for z, r in zip(idx, res) if len(r["consensus"]) >= max(1, min_length) and -2 in r["keys"]]
+        got = _mapping.map_batch([(r["consensus"], [None if x is None else x["seq"]
+                                                    for x in filtered[z][r["keys"].index(-2):]]) for z, r in todo],
+                                 engine=engine)
+        past = {z: g for (z, _), g in zip(todo, got)}
     for z, r in zip(idx, res):
         draft = r["consensus"]
         if len(draft) < min_length:
@@ -143,14 +172,17 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None):
         reads = []
         for i, key in enumerate(r["keys"]):
             if key == -2:
-                break   # past maxPoaCov: Consensus.h's loop stopped before this read
+                # past maxPoaCov: Consensus.h's loop stopped before this read
+                if z in past:
+                    reads += _past_cap(filtered[z][i:], past[z], min_length)
+                break
             mr = extract_mapped_read(filtered[z][i], r["summaries"][key], min_length) if key >= 0 else None
             reads.append(mr if mr is not None else {"seq": None, "strand": 0, "ts": 0, "te": 0, "full_pass": False})
         out[z] = (None, {"draft": draft, "snr": list(chunks[z]["snr"]), "reads": reads})
     return out
 
 
-def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None):
+def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -159,6 +191,8 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None):
     by the POA, rejected by ExtractMappedRead, past the maxPoaCov stop, or the ZMW ended earlier).
     "add_order" lists the subread indices in AddRead order (FilterReads' stable order, Consensus.h:281):
     the order of ZScores() and of the ccs.bam zs tag.
+    map_past_cap (pbccs_ccs_batch_ex): the reads past the maxPoaCov stop are placed on the draft on the GPU
+    (mapping.map_to_draft's aligner) and reach AddRead like the POA's reads, in FilterReads' order.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -219,8 +253,15 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None):
         outs["add_order"][:n] = order.ctypes.data + 4 * f0
     opts = settings._c()
     mc = 2**62 if max_poa_coverage is None else int(max_poa_coverage)
-    L.check(L.load().pbccs_ccs_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n, mc,
-                                     ctypes.byref(opts), ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    if map_past_cap:
+        co = L.CCcsOptions(mc, 1)
+        L.check(L.load().pbccs_ccs_batch_ex(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                            ctypes.byref(co), ctypes.byref(opts),
+                                            ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    else:
+        L.check(L.load().pbccs_ccs_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n, mc,
+                                         ctypes.byref(opts),
+                                         ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
     del blob, joined, ptrs, lens, flags   # the inputs lived until the call returned
     pol = outs["polish"]
     status, clen = pol["status"][:n].tolist(), pol["consensus_len"][:n].tolist()

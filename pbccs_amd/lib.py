@@ -183,6 +183,25 @@ class CAlignStats(ctypes.Structure):
                 ("bytes", ctypes.c_double), ("groups", ctypes.c_longlong)]
 
 
+class CMapInput(ctypes.Structure):
+    _fields_ = [("draft", ctypes.c_char_p), ("draft_len", ctypes.c_int), ("seqs", ctypes.POINTER(ctypes.c_char_p)),
+                ("lens", ctypes.POINTER(ctypes.c_int)), ("n_reads", ctypes.c_int)]
+
+
+class CMapOutput(ctypes.Structure):
+    _fields_ = [("mapped", ctypes.POINTER(ctypes.c_int)), ("rc", ctypes.POINTER(ctypes.c_int)),
+                ("extents", ctypes.POINTER(ctypes.c_int)), ("score", ctypes.POINTER(ctypes.c_int))]
+
+
+class CMapStats(ctypes.Structure):
+    _fields_ = [("jobs", ctypes.c_longlong), ("cells", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("strips", ctypes.c_longlong), ("device_ms", ctypes.c_double)]
+
+
+class CCcsOptions(ctypes.Structure):
+    _fields_ = [("max_poa_coverage", ctypes.c_longlong), ("map_past_cap", ctypes.c_int)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -290,6 +309,12 @@ SIGNATURES = {
     "pbccs_align_stats_get": (I, [P, ctypes.POINTER(CAlignStats), I]),
     "pbccs_ccs_batch": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.c_longlong, ctypes.POINTER(CPolishOptions),
                             ctypes.POINTER(CCcsOutput)]),
+    # MapToDraft and the capped ccs that keeps every pass
+    "pbccs_map_batch": (I, [P, ctypes.POINTER(CMapInput), I, ctypes.c_float, ctypes.POINTER(CMapOutput)]),
+    "pbccs_map_stats_get": (I, [P, ctypes.POINTER(CMapStats), I]),
+    "pbccs_ccs_options_default": (None, [ctypes.POINTER(CCcsOptions)]),
+    "pbccs_ccs_batch_ex": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                               ctypes.POINTER(CPolishOptions), ctypes.POINTER(CCcsOutput)]),
 }
 
 

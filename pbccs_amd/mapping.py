@@ -1,0 +1,87 @@
+"""MapToDraft on the GPU: placing reads on a finished draft (pbccs_map_batch).
+
+What SparsePoa::OrientAndAddRead followed by FindConsensus reports for a read on a graph that holds only the draft
+as one unbranched path -- orientation, extent on the read, extent on the draft -- from a LOCAL alignment of the
+read against the linear draft (k_map_fill: no graph, no stored matrix, no traceback).  It is what lets a POA
+capped by max_poa_coverage keep the reads past the cap (driver.ccs_batch(..., map_past_cap=True)).
+There is no CPU fallback: without the library or a GPU these raise."""
+import ctypes
+
+from . import lib as _L
+from .lib import load
+
+
+def _engine(engine):
+    if engine is None:
+        from . import default_engine
+        engine = default_engine()
+    return engine
+
+
+def map_batch(zmws, min_score_to_add=0.0, engine=None):
+    """zmws: [(draft, [read or None, ...])].  Returns per ZMW a list with one entry per read: None for a read that
+    was not mapped (no read, or both orientations below min_score_to_add), else {"rc", "read": (b, e), "tpl":
+    (b, e), "score"} -- the PoaAlignmentSummary driver.extract_mapped_read takes, plus the alignment score.
+
+    Marshalling is flat, as poa.poa_batch's: all sequences in one buffer with a pointer table, all outputs in
+    shared arrays, the per-ZMW structs written column-wise."""
+    import numpy as np
+    from .quiver import _struct_dtype
+    eng = _engine(engine)
+    n = len(zmws)
+    counts = np.fromiter((len(reads) for _, reads in zmws), dtype=np.int64, count=n)
+    drafts = [d.encode() for d, _ in zmws]
+    enc = [b"" if r is None else r.encode() for _, reads in zmws for r in reads]
+    nr = len(enc)
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int32, count=nr)
+    dlens = np.fromiter((len(d) for d in drafts), dtype=np.int64, count=n)
+    blob = ctypes.create_string_buffer(b"".join(enc) + b"".join(drafts), max(1, int(lens.sum()) + int(dlens.sum())))
+    starts = np.zeros(nr + 1, dtype=np.int64)
+    np.cumsum(lens, out=starts[1:])
+    ptrs = (ctypes.addressof(blob) + starts[:-1]).astype(np.uint64)
+    ptrs[lens == 0] = 0                                   # NULL: no read
+    dstarts = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(dlens, out=dstarts[1:])
+    first = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=first[1:])
+    mapped = np.zeros(max(1, nr), dtype=np.int32)
+    rc = np.zeros(max(1, nr), dtype=np.int32)
+    score = np.zeros(max(1, nr), dtype=np.int32)
+    ext = np.zeros(max(4, 4 * nr), dtype=np.int32)
+    ins = np.zeros(max(1, n), dtype=_struct_dtype(_L.CMapInput))
+    outs = np.zeros(max(1, n), dtype=_struct_dtype(_L.CMapOutput))
+    if n:
+        f0 = first[:-1]
+        ins["draft"][:n] = ctypes.addressof(blob) + int(starts[-1]) + dstarts[:-1]
+        ins["draft_len"][:n] = dlens
+        ins["seqs"][:n] = ptrs.ctypes.data + 8 * f0
+        ins["lens"][:n] = lens.ctypes.data + 4 * f0
+        ins["n_reads"][:n] = counts
+        outs["mapped"][:n] = mapped.ctypes.data + 4 * f0
+        outs["rc"][:n] = rc.ctypes.data + 4 * f0
+        outs["extents"][:n] = ext.ctypes.data + 16 * f0
+        outs["score"][:n] = score.ctypes.data + 4 * f0
+    _L.check(load().pbccs_map_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CMapInput)), n,
+                                    float(min_score_to_add), ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CMapOutput))))
+    m_l, rc_l, sc_l, ext_l = mapped.tolist(), rc.tolist(), score.tolist(), ext.tolist()
+    firsts, cnts = first.tolist(), counts.tolist()
+    res = []
+    for z in range(n):
+        f = firsts[z]
+        res.append([{"rc": bool(rc_l[k]), "read": (ext_l[4 * k], ext_l[4 * k + 1]),
+                     "tpl": (ext_l[4 * k + 2], ext_l[4 * k + 3]), "score": sc_l[k]} if m_l[k] else None
+                    for k in range(f, f + cnts[z])])
+    return res
+
+
+def map_to_draft(draft, reads, min_score_to_add=0.0, engine=None):
+    """MapToDraft(draft, reads, minScoreToAdd): one entry per read, None when it was not mapped, else the summary
+    {"rc", "read", "tpl", "score"}."""
+    return map_batch([(draft, list(reads))], min_score_to_add, engine)[0]
+
+
+def map_stats(engine=None, reset=False):
+    eng = _engine(engine)
+    s = _L.CMapStats()
+    _L.check(load().pbccs_map_stats_get(eng._h, ctypes.byref(s), 1 if reset else 0))
+    return {k: getattr(s, k) for k, _ in _L.CMapStats._fields_}
