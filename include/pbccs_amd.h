@@ -721,6 +721,58 @@ void pbccs_ccs_options_default(pbccs_ccs_options* o);   /* no cap, map_past_cap 
 int pbccs_ccs_batch_ex(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
                        const pbccs_polish_options* opts, pbccs_ccs_output* out);
 
+/* ---- SparseAlign: K-mer seeds, their chain, alignable ranges -------------------------------------------
+ * PacBio::CCS::SparseAlign<K>(seq1, seq2) (include/pacbio/ccs/SparseAlignment.h:275-310, src/ChainSeeds.cpp with
+ * matchReward 3) for n independent pairs per call, equal to the reference anchor for anchor: every K-mer of the
+ * query that is not a homopolymer seeds (h, v) at each target position holding it; the chain is the reference's
+ * sparse dynamic programme (visible-left, visible-above and column-set candidates, in that order of precedence,
+ * a later one only when strictly greater; the first best end in (v, h) order).  target is seq1 (H), query seq2
+ * (V).  All of it runs on the device (k_sparse_count / _index / _visible / _sweep / _ranges).
+ * Defined here rather than copied: an empty query gives an empty chain (the reference dereferences it), a letter
+ * outside upper-case ACGT is that pair's PBCCS_EINVAL (SeqAn would read it as some base), and K is a parameter,
+ * 4 <= k <= 8 (the product uses 6, the reference's tests 5). */
+typedef struct {
+    const char* target;
+    int target_len;
+    const char* query;
+    int query_len;
+    int reverse_complement;   /* != 0: chain the query's reverse complement (formed on the device) */
+    int* anchors;             /* 2 * anchor_cap ints: (h, v) per anchor, ascending in both.  A chain never has more
+                                 than min(target_len, query_len) - k + 1 anchors */
+    int anchor_cap;
+    int* ranges;              /* NULL, or 2 * target_len ints: [begin, end) of the query rows alignable to each target
+                                 position, as SdpRangeFinder::InitRangeFinder (RangeFinder.cpp:71-165, WIDTH 30)
+                                 reports them for a graph holding only the target as one unbranched path; positions
+                                 before the first or after the last anchor inherit the inverted interval of
+                                 RangeUnion({}), and with no anchor at all every position is (query_len, 0) */
+} pbccs_sparse_align_input;
+
+typedef struct {
+    int status;          /* PBCCS_OK, or this pair's PBCCS_EINVAL / PBCCS_EOOM / PBCCS_ERANGE */
+    int n_anchors;       /* chain length; with PBCCS_ERANGE (anchor_cap too small) nothing was written */
+    long long n_seeds;   /* seeds found (also for a pair over the cap) */
+    long long score;     /* the chain's score, 0 for an empty chain */
+} pbccs_sparse_align_output;
+
+/* PBCCS_EINVAL before any device work: k outside 4..8, a negative length, a null sequence with a positive length.
+ * Per pair: PBCCS_EINVAL for a letter outside ACGT or a sequence longer than 1048576; PBCCS_EOOM, known after
+ * the counting pass and with no further device work for that pair, when it has more seeds than the cap
+ * (PBCCS_SPARSE_MAX_SEEDS, default 4194304: a seed takes 24 bytes on the device) or its own arrays exceed half
+ * the workspace budget (PBCCS_SPARSE_WORKSPACE_KB, default 1048576), into which the batch is split.  The other
+ * pairs complete, the engine stays usable, and the call returns the first failing pair's status. */
+int pbccs_sparse_align_batch(pbccs_engine* eng, int k, const pbccs_sparse_align_input* in, int n,
+                             pbccs_sparse_align_output* out);
+
+/* SparseAlign work since the last reset: pairs given, seeds found, anchors returned, kernel launches, device ms
+ * (profiling on), and over the pairs that asked for ranges the cells inside them and the full
+ * target_len * (query_len + 1) cells a POA column fill visits. */
+typedef struct {
+    long long jobs, seeds, anchors, launches;
+    double device_ms;
+    long long range_cells, full_cells;
+} pbccs_sparse_align_stats;
+int pbccs_sparse_align_stats_get(pbccs_engine* eng, pbccs_sparse_align_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 //   PacBio::CCS::PoaAlignmentSummary / PoaAlignmentOptions include/pacbio/ccs/SparsePoa.h:57-85
 //   PacBio::CCS::SparsePoa                                 include/pacbio/ccs/SparsePoa.h:87-131
 //   ConsensusCore::PoaConsensus::FindConsensus             ConsensusCore/include/ConsensusCore/Poa/PoaConsensus.hpp:60-97
+//   PacBio::CCS::SparseAlign<K>, SdpRangeFinder::FindAnchors  SparseAlignment.hpp (included below)
 // Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch).
 #pragma once
 
@@ -19,6 +20,7 @@
 
 #include "AlignMode.hpp"
 #include "ConsensusCore.hpp"
+#include "SparseAlignment.hpp"
 
 namespace ConsensusCore {
 

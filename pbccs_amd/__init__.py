@@ -311,6 +311,7 @@ from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac,
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
                     TargetToQueryPositions, UnsupportedFeatureError, align_batch, align_stats)
 from .mapping import map_batch, map_stats, map_to_draft  # noqa: E402,F401
+from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa: E402,F401
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -28,6 +28,7 @@
 #include "map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
+#include "sparse_kernels.hpp"
 
 using namespace pbccs;
 
@@ -105,6 +106,15 @@ struct pbccs_engine {
         if (!mapper) mapper.reset(new map::MapRunner(device));
         mapper->profiling = profiling;
         return *mapper;
+    }
+    // SparseAlign's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<sparse::SparseRunner> sparseRunner;
+    std::mutex sparseMu;
+    sparse::SparseRunner& Sparse()
+    {
+        if (!sparseRunner) sparseRunner.reset(new sparse::SparseRunner(device));
+        sparseRunner->profiling = profiling;
+        return *sparseRunner;
     }
     Workspace* Slot(int s)
     {
@@ -2246,6 +2256,54 @@ int pbccs_map_stats_get(pbccs_engine* eng, pbccs_map_stats* out, int reset)
         const map::MapStats s = eng->mapper ? eng->mapper->stats : map::MapStats();
         *out = pbccs_map_stats{s.jobs, s.cells, s.launches, s.strips, s.deviceMs};
         if (reset && eng->mapper) eng->mapper->stats = map::MapStats();
+        return PBCCS_OK;
+    });
+}
+
+// ---- SparseAlign (sparse_kernels.hpp) -----------------------------------------------------------------------
+int pbccs_sparse_align_batch(pbccs_engine* eng, int k, const pbccs_sparse_align_input* in, int n,
+                             pbccs_sparse_align_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    if (k < sparse::kMinK || k > sparse::kMaxK) return fail(PBCCS_EINVAL, "SparseAlign: k must be 4..8");
+    for (int g = 0; g < n; ++g) {
+        const pbccs_sparse_align_input& s = in[g];
+        if (s.target_len < 0 || s.query_len < 0 || (s.target_len > 0 && !s.target) || (s.query_len > 0 && !s.query) ||
+            s.anchor_cap < 0 || (s.anchor_cap > 0 && !s.anchors))
+            return fail(PBCCS_EINVAL, "bad pbccs_sparse_align_input (NULL buffer or negative length)");
+    }
+    return guarded([&] {
+        std::vector<sparse::SparseInput> jobs(n);
+        for (int g = 0; g < n; ++g)
+            jobs[g] = sparse::SparseInput{in[g].target, in[g].target_len, in[g].query, in[g].query_len,
+                                          in[g].reverse_complement, in[g].anchors, in[g].anchor_cap, in[g].ranges};
+        std::vector<sparse::SparseResult> res;
+        {
+            std::lock_guard<std::mutex> lk(eng->sparseMu);
+            eng->Sparse().Run(k, jobs.data(), n, &res);
+        }
+        int first = PBCCS_OK;
+        for (int g = 0; g < n; ++g) {
+            out[g] = pbccs_sparse_align_output{res[g].status, res[g].nAnchors, res[g].nSeeds, res[g].score};
+            if (first == PBCCS_OK) first = res[g].status;
+        }
+        if (first == PBCCS_EINVAL) return fail(first, "SparseAlign: a letter outside ACGT, or a sequence longer than 1048576");
+        if (first == PBCCS_EOOM)
+            return fail(first, "SparseAlign: a pair exceeds the seed cap (PBCCS_SPARSE_MAX_SEEDS) or the workspace "
+                               "(PBCCS_SPARSE_WORKSPACE_KB)");
+        if (first == PBCCS_ERANGE) return fail(first, "SparseAlign: a chain is longer than its anchor buffer");
+        return first;
+    });
+}
+
+int pbccs_sparse_align_stats_get(pbccs_engine* eng, pbccs_sparse_align_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->sparseMu);
+        const sparse::SparseStats s = eng->sparseRunner ? eng->sparseRunner->stats : sparse::SparseStats();
+        *out = pbccs_sparse_align_stats{s.jobs, s.seeds, s.anchors, s.launches, s.deviceMs, s.rangeCells, s.fullCells};
+        if (reset && eng->sparseRunner) eng->sparseRunner->stats = sparse::SparseStats();
         return PBCCS_OK;
     });
 }

@@ -202,6 +202,24 @@ class CCcsOptions(ctypes.Structure):
     _fields_ = [("max_poa_coverage", ctypes.c_longlong), ("map_past_cap", ctypes.c_int)]
 
 
+class CSparseAlignInput(ctypes.Structure):
+    _fields_ = [("target", ctypes.c_char_p), ("target_len", ctypes.c_int), ("query", ctypes.c_char_p),
+                ("query_len", ctypes.c_int), ("reverse_complement", ctypes.c_int),
+                ("anchors", ctypes.POINTER(ctypes.c_int)), ("anchor_cap", ctypes.c_int),
+                ("ranges", ctypes.POINTER(ctypes.c_int))]
+
+
+class CSparseAlignOutput(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("n_anchors", ctypes.c_int), ("n_seeds", ctypes.c_longlong),
+                ("score", ctypes.c_longlong)]
+
+
+class CSparseAlignStats(ctypes.Structure):
+    _fields_ = [("jobs", ctypes.c_longlong), ("seeds", ctypes.c_longlong), ("anchors", ctypes.c_longlong),
+                ("launches", ctypes.c_longlong), ("device_ms", ctypes.c_double),
+                ("range_cells", ctypes.c_longlong), ("full_cells", ctypes.c_longlong)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -315,6 +333,10 @@ SIGNATURES = {
     "pbccs_ccs_options_default": (None, [ctypes.POINTER(CCcsOptions)]),
     "pbccs_ccs_batch_ex": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
                                ctypes.POINTER(CPolishOptions), ctypes.POINTER(CCcsOutput)]),
+    # SparseAlign: seeds, chain, alignable ranges
+    "pbccs_sparse_align_batch": (I, [P, I, ctypes.POINTER(CSparseAlignInput), I,
+                                     ctypes.POINTER(CSparseAlignOutput)]),
+    "pbccs_sparse_align_stats_get": (I, [P, ctypes.POINTER(CSparseAlignStats), I]),
 }
 
 
