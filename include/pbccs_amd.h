@@ -773,6 +773,68 @@ typedef struct {
 } pbccs_sparse_align_stats;
 int pbccs_sparse_align_stats_get(pbccs_engine* eng, pbccs_sparse_align_stats* out, int reset);
 
+/* ---- Banded POA fill: reads aligned to the graph inside SdpRangeFinder's ranges ------------------------
+ * An opt-in; with the switch off every call is what it was.  LOCAL alignments only.  Before
+ * each TryAddRead of a graph that holds a read: the consensus path (ConsensusPath(LOCAL, -INT_MAX)) and its
+ * sequence; anchors = SparseAlign<6>(css, read) on the device; per vertex the range [B, E) of
+ * SdpRangeFinder::InitRangeFinder (RangeFinder.cpp:71-165, WIDTH 30) on the branching graph.  A column holds the
+ * rows B <= i <= min(E, I); a cell outside its column's band does not exist and offers no candidate, every
+ * existing cell keeps LOCAL's Start, candidate order and the strict '>' are those of the full fill, and the exit
+ * takes the first maximal existing row of the best column (ties to the lower vertex id).  An alignment without
+ * anchors (which includes a read or consensus shorter than 6), with a letter outside ACGT, or whose seeding ran
+ * out of memory takes the full fill and is counted as a fallback; its other orientation and the other ZMWs stay
+ * banded. */
+typedef struct {
+    long long max_coverage;   /* >= 1 */
+    int min_coverage;         /* as pbccs_poa_batch */
+    int banded;
+} pbccs_poa_options;
+void pbccs_poa_options_default(pbccs_poa_options* o);   /* no cap, min_coverage -1, banded 0 */
+/* pbccs_poa_batch with options; opts NULL is the defaults, banded 0 is pbccs_poa_batch */
+int pbccs_poa_batch_ex(pbccs_engine* eng, const pbccs_poa_input* in, int n, const pbccs_poa_options* opts,
+                       pbccs_poa_output* out);
+/* pbccs_sparse_poa_orient_and_add_read of this handle fills banded from now on (on != 0) */
+int pbccs_sparse_poa_set_banded(pbccs_sparse_poa* p, int on);
+
+/* What the range finder sees for one read (rc != 0: its reverse complement) against the handle's current graph,
+ * which must hold a read: the consensus path as vertex ids (css_path, css_cap ints, *css_len), the anchors as
+ * (consensus position, read position) pairs (anchors, 2 * anchor_cap ints, *n_anchors) and [B, E) per vertex id
+ * (ranges, 2 * range_cap ints, *n_vertices; $ = vertex 1 has no column and reads (0, 0)).  *fallback != 0: the
+ * alignment would take the full fill (no anchors, a foreign letter, seeding out of memory); anchors and ranges
+ * are then not written and their counts are 0.  PBCCS_ERANGE when a buffer is too small, counts set. */
+int pbccs_sparse_poa_alignable_ranges(pbccs_sparse_poa* p, const char* seq, int len, int rc, int* css_path,
+                                      int css_cap, int* css_len, int* anchors, int anchor_cap, int* n_anchors,
+                                      int* ranges, int range_cap, int* n_vertices, int* fallback);
+
+/* Moves of a traceback step (PoaGraphImpl.hpp:45-55) */
+#define PBCCS_POA_MOVE_START 1
+#define PBCCS_POA_MOVE_END 2
+#define PBCCS_POA_MOVE_MATCH 3
+#define PBCCS_POA_MOVE_MISMATCH 4
+#define PBCCS_POA_MOVE_DELETE 5
+#define PBCCS_POA_MOVE_EXTRA 6
+/* TryAddRead without the commit: the exit score of the read (rc != 0: of its reverse complement) against the
+ * handle's current graph, which must hold a read, and the traceback in the device's order -- steps[3 k] the
+ * vertex, steps[3 k + 1] the move that reached the visited cell, steps[3 k + 2] the cell's row; step 0 is the End
+ * move into $ (vertex 1, row len), the last step the Start move.  banded != 0 fills inside the ranges (or takes the full fill where the rules above
+ * send the alignment back).  PBCCS_ERANGE when cap (in steps) is too small, *n_steps set. */
+int pbccs_sparse_poa_try_add_read(pbccs_sparse_poa* p, const char* seq, int len, int rc, int banded, float* score,
+                                  int* steps, int cap, int* n_steps);
+
+/* pbccs_ccs_batch_ex with the POA's options: poa NULL or poa->banded 0 is pbccs_ccs_batch_ex.  Only poa->banded
+ * is read: the coverage cap comes from ccs, the draft's min_coverage is Consensus.h's rule. */
+int pbccs_ccs_batch_ex2(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_polish_options* opts, pbccs_ccs_output* out);
+
+/* Banded-fill work since the last reset: alignments filled banded, alignments that fell back to the full fill,
+ * the cells inside the bands and the full cols x (I + 1) of the same alignments, seeds and anchors of the
+ * seeding, device ms by phase (profiling on) and the score bytes the banded fills wrote. */
+typedef struct {
+    long long banded_alignments, fallbacks, band_cells, full_cells, seeds, anchors;
+    double seed_ms, ranges_ms, fill_ms, trace_ms, score_bytes;
+} pbccs_poa_band_stats;
+int pbccs_poa_band_stats_get(pbccs_engine* eng, pbccs_poa_band_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,12 @@
 //   PacBio::CCS::SdpRangeFinder::FindAnchors                                 src/SparsePoa.cpp:56-64
 //   ConsensusCore::detail::SdpAnchor / SdpAnchorVector                       ConsensusCore/Poa/RangeFinder.hpp:20-21
 // Beyond the reference: SdpRangeFinder::FindAlignableRanges, the rows InitRangeFinder would report for a graph that
-// holds only the consensus as one unbranched path.
+// holds only the consensus as one unbranched path; InitRangeFinder / FindAlignableRange (RangeFinder.cpp:71-171) take
+// a SparsePoa (SparsePoa.hpp) in place of the graph, consensus path and consensus sequence, which stay in the engine.
 #pragma once
 
 #include <algorithm>
+#include <stdexcept>
 #include <string>
 #include <utility>
 #include <vector>
@@ -72,6 +74,27 @@ public:
         for (size_t p = 0; p < consensusSequence.size(); ++p) ranges.emplace_back(flat[2 * p], flat[2 * p + 1]);
         return ranges;
     }
+
+    // InitRangeFinder over a SparsePoa's current graph (which must hold a read) for one read; false when the
+    // alignment would take the full fill, and FindAlignableRange then has nothing to report.
+    template <class TSparsePoa>
+    bool InitRangeFinder(const TSparsePoa& poa, const std::string& readSequence, bool reverseComplement = false)
+    {
+        return poa.AlignableRanges(readSequence, reverseComplement, &consensusPath_, &anchors_, &rangeByVertex_);
+    }
+    // [begin, end) of the read rows alignable to a vertex of that graph
+    std::pair<int, int> FindAlignableRange(size_t vertex) const
+    {
+        if (vertex >= rangeByVertex_.size()) throw std::out_of_range("FindAlignableRange: no such vertex");
+        return rangeByVertex_[vertex];
+    }
+    const std::vector<int>& ConsensusPath() const { return consensusPath_; }
+    const ConsensusCore::detail::SdpAnchorVector& Anchors() const { return anchors_; }
+
+private:
+    std::vector<int> consensusPath_;
+    ConsensusCore::detail::SdpAnchorVector anchors_;
+    std::vector<std::pair<int, int>> rangeByVertex_;
 };
 
 }  // namespace CCS

@@ -9,7 +9,10 @@
 //   PacBio::CCS::SparsePoa                                 include/pacbio/ccs/SparsePoa.h:87-131
 //   ConsensusCore::PoaConsensus::FindConsensus             ConsensusCore/include/ConsensusCore/Poa/PoaConsensus.hpp:60-97
 //   PacBio::CCS::SparseAlign<K>, SdpRangeFinder::FindAnchors  SparseAlignment.hpp (included below)
-// Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch).
+// Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch); a banded
+// switch on SparsePoa (alignments filled inside SdpRangeFinder's ranges, which the reference computes and then
+// ignores), with AlignableRanges / TryAddRead to look at one alignment, and SdpRangeFinder::InitRangeFinder /
+// FindAlignableRange over a SparsePoa's graph (SparseAlignment.hpp).
 #pragma once
 
 #include <climits>
@@ -90,6 +93,8 @@ public:
     using ReadKey = int;
 
     SparsePoa() { ConsensusCore::detail::Check(pbccs_sparse_poa_create(ConsensusCore::detail::DefaultEngine(), &h_)); }
+    // banded: every alignment is filled inside the range finder's ranges (pbccs_sparse_poa_set_banded)
+    explicit SparsePoa(bool banded) : SparsePoa() { SetBanded(banded); }
     ~SparsePoa() { pbccs_sparse_poa_destroy(h_); }
     SparsePoa(const SparsePoa&) = delete;
     SparsePoa& operator=(const SparsePoa&) = delete;
@@ -128,6 +133,60 @@ public:
         return std::make_shared<const ConsensusCore::PoaConsensus>(out);
     }
 
+    void SetBanded(bool on)
+    {
+        ConsensusCore::detail::Check(pbccs_sparse_poa_set_banded(h_, on ? 1 : 0));
+        banded_ = on;
+    }
+    bool Banded() const { return banded_; }
+
+    // What the range finder sees for this read (reverseComplement: its reverse complement) against the current
+    // graph: the consensus path as vertex ids, the anchors as (consensus position, read position) and [B, E) per
+    // vertex id.  false: the alignment would take the full fill (no anchors, a foreign letter, seeding out of
+    // memory); anchors and ranges are then empty.
+    bool AlignableRanges(const std::string& readSequence, bool reverseComplement, std::vector<int>* cssPath,
+                         std::vector<std::pair<size_t, size_t>>* anchors,
+                         std::vector<std::pair<int, int>>* ranges) const
+    {
+        const int nv = (int)bases_ + 2, na = (int)readSequence.size() + 1;
+        std::vector<int> css(nv), an(2 * (size_t)na), rg(2 * (size_t)nv);
+        int nc = 0, nan = 0, nr = 0, fallback = 0;
+        ConsensusCore::detail::Check(pbccs_sparse_poa_alignable_ranges(
+            h_, readSequence.data(), (int)readSequence.size(), reverseComplement ? 1 : 0, css.data(), nv, &nc, an.data(),
+            na, &nan, rg.data(), nv, &nr, &fallback));
+        if (cssPath) cssPath->assign(css.begin(), css.begin() + nc);
+        if (anchors) {
+            anchors->clear();
+            for (int a = 0; a < nan; ++a) anchors->emplace_back((size_t)an[2 * a], (size_t)an[2 * a + 1]);
+        }
+        if (ranges) {
+            ranges->clear();
+            for (int v = 0; v < nr; ++v) ranges->emplace_back(rg[2 * v], rg[2 * v + 1]);
+        }
+        return fallback == 0;
+    }
+
+    // TryAddRead without the commit: the exit score, and per step of the traceback (vertex, move, row)
+    struct TraceStep {
+        int Vertex, Move, Row;
+    };
+    float TryAddRead(const std::string& readSequence, bool reverseComplement, bool banded,
+                     std::vector<TraceStep>* steps = nullptr) const
+    {
+        const int cap = (int)(readSequence.size() + bases_) + 4;
+        std::vector<int> raw(3 * (size_t)cap);
+        float score = 0;
+        int n = 0;
+        ConsensusCore::detail::Check(pbccs_sparse_poa_try_add_read(h_, readSequence.data(), (int)readSequence.size(),
+                                                                   reverseComplement ? 1 : 0, banded ? 1 : 0, &score,
+                                                                   raw.data(), cap, &n));
+        if (steps) {
+            steps->clear();
+            for (int k = 0; k < n; ++k) steps->push_back(TraceStep{raw[3 * k], raw[3 * k + 1], raw[3 * k + 2]});
+        }
+        return score;
+    }
+
     std::string ToGraphViz(int flags = 0, int minCoverage = -INT_MAX) const
     {
         int len = 0;
@@ -142,6 +201,7 @@ private:
     pbccs_sparse_poa* h_ = nullptr;
     int reads_ = 0;
     size_t bases_ = 0;
+    bool banded_ = false;
 };
 
 // MapToDraft(draft, reads, minScoreToAdd): what OrientAndAddRead + FindConsensus would report for each read on a

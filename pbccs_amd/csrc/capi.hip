@@ -1948,6 +1948,7 @@ int pbccs_diploid_stats_get(pbccs_engine* eng, pbccs_diploid_stats* out, int res
 struct pbccs_sparse_poa {
     pbccs_engine* eng;
     poa::ZmwPoa z;
+    bool banded = false;   // pbccs_sparse_poa_set_banded
 };
 
 namespace {
@@ -1962,8 +1963,8 @@ int put_text(const std::string& s, char* out, int cap, int* len)
 
 }  // namespace
 
-int pbccs_poa_batch(pbccs_engine* eng, const pbccs_poa_input* in, int n, long long max_coverage, int min_coverage,
-                    pbccs_poa_output* out)
+static int poa_batch_impl(pbccs_engine* eng, const pbccs_poa_input* in, int n, long long max_coverage,
+                          int min_coverage, bool banded, pbccs_poa_output* out)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
     return guarded([&] {
@@ -1984,7 +1985,8 @@ int pbccs_poa_batch(pbccs_engine* eng, const pbccs_poa_input* in, int n, long lo
         std::vector<std::vector<char>> rc;
         {
             std::lock_guard<std::mutex> lk(eng->poaMu);
-            poa::PoaBatch(eng->PoaRunners(), reads, max_coverage, min_coverage, &css, &keys, &rc, &ext);
+            poa::PoaBatch(eng->PoaRunners(), reads, max_coverage, min_coverage, &css, &keys, &rc, &ext, nullptr,
+                          banded);
         }
         bool range = false;
         for (int z = 0; z < n; ++z) {
@@ -2005,11 +2007,99 @@ int pbccs_poa_batch(pbccs_engine* eng, const pbccs_poa_input* in, int n, long lo
     });
 }
 
+int pbccs_poa_batch(pbccs_engine* eng, const pbccs_poa_input* in, int n, long long max_coverage, int min_coverage,
+                    pbccs_poa_output* out)
+{
+    return poa_batch_impl(eng, in, n, max_coverage, min_coverage, false, out);
+}
+
+void pbccs_poa_options_default(pbccs_poa_options* o)
+{
+    if (!o) return;
+    o->max_coverage = std::numeric_limits<long long>::max();
+    o->min_coverage = -1;
+    o->banded = 0;
+}
+
+int pbccs_poa_batch_ex(pbccs_engine* eng, const pbccs_poa_input* in, int n, const pbccs_poa_options* opts,
+                       pbccs_poa_output* out)
+{
+    pbccs_poa_options o;
+    if (opts) o = *opts;
+    else pbccs_poa_options_default(&o);
+    return poa_batch_impl(eng, in, n, o.max_coverage, o.min_coverage, o.banded != 0, out);
+}
+
 int pbccs_sparse_poa_create(pbccs_engine* eng, pbccs_sparse_poa** out)
 {
     if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
     return guarded([&] {
         *out = new pbccs_sparse_poa{eng, poa::ZmwPoa()};
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_sparse_poa_set_banded(pbccs_sparse_poa* p, int on)
+{
+    if (!p) return fail(PBCCS_EINVAL, "bad argument");
+    p->banded = on != 0;
+    return PBCCS_OK;
+}
+
+int pbccs_sparse_poa_alignable_ranges(pbccs_sparse_poa* p, const char* seq, int len, int rc, int* css_path,
+                                      int css_cap, int* css_len, int* anchors, int anchor_cap, int* n_anchors,
+                                      int* ranges, int range_cap, int* n_vertices, int* fallback)
+{
+    if (!p || (!seq && len > 0) || len < 0 || !css_len || !n_anchors || !n_vertices || !fallback)
+        return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        if (p->z.graph.NumReads() == 0) return fail(PBCCS_ESTATE, "the graph holds no read");
+        poa::RangeReport rep;
+        {
+            std::lock_guard<std::mutex> lk(p->eng->poaMu);
+            p->eng->Poa().Ranges(&p->z.graph, std::string(seq ? seq : "", len), rc != 0, &rep);
+        }
+        *css_len = (int)rep.cssPath.size();
+        *n_anchors = (int)rep.anchors.size() / 2;
+        *n_vertices = (int)rep.ranges.size() / 2;
+        *fallback = rep.ranges.empty() ? 1 : 0;
+        if (*css_len > css_cap || *n_anchors > anchor_cap || *n_vertices > range_cap ||
+            (!css_path && *css_len) || (!anchors && *n_anchors) || (!ranges && *n_vertices))
+            return fail(PBCCS_ERANGE, "buffer too small");
+        if (*css_len) memcpy(css_path, rep.cssPath.data(), rep.cssPath.size() * sizeof(int));
+        if (*n_anchors) memcpy(anchors, rep.anchors.data(), rep.anchors.size() * sizeof(int));
+        if (*n_vertices) memcpy(ranges, rep.ranges.data(), rep.ranges.size() * sizeof(int));
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_sparse_poa_try_add_read(pbccs_sparse_poa* p, const char* seq, int len, int rc, int banded, float* score,
+                                  int* steps, int cap, int* n_steps)
+{
+    if (!p || !seq || len <= 0 || !score || !n_steps || cap < 0) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        if (p->z.graph.NumReads() == 0) return fail(PBCCS_ESTATE, "the graph holds no read");
+        poa::AlignRequest rq{&p->z.graph, std::string(seq, len), poa::kLocal, true, 0.f, banded != 0, rc ? 1 : 0};
+        std::vector<poa::AlignRequest> req{rq};
+        std::vector<poa::AlignResult> res;
+        {
+            std::lock_guard<std::mutex> lk(p->eng->poaMu);
+            p->eng->Poa().Align(req, &res);
+        }
+        const poa::AlignResult& R = res[0];
+        *score = R.score[rc ? 1 : 0];
+        *n_steps = (int)R.steps.size();
+        if (*n_steps > cap || (!steps && *n_steps)) return fail(PBCCS_ERANGE, "buffer too small");
+        int row = len;   // the cell each step stands on: $'s row, the End move's source row, then as the moves go
+        for (int k = 0; k < *n_steps; ++k) {
+            const int mv = (int)(R.steps[k] >> 28);
+            steps[3 * k] = (int)(R.steps[k] & poa::kStepVertexMask);
+            steps[3 * k + 1] = mv;
+            steps[3 * k + 2] = row;
+            if (mv == poa::kEnd) row = R.head.endRow;
+            else if (mv == poa::kStart) row = 0;
+            else if (mv != poa::kDelete) row--;
+        }
         return PBCCS_OK;
     });
 }
@@ -2034,7 +2124,8 @@ int pbccs_sparse_poa_orient_and_add_read(pbccs_sparse_poa* p, const char* seq, i
             *key = 0;
             return PBCCS_OK;
         }
-        std::vector<poa::AlignRequest> req{poa::AlignRequest{&p->z.graph, s, poa::kLocal, true, min_score_to_add}};
+        std::vector<poa::AlignRequest> req{
+            poa::AlignRequest{&p->z.graph, s, poa::kLocal, true, min_score_to_add, p->banded}};
         std::vector<poa::AlignResult> res;
         {
             std::lock_guard<std::mutex> lk(p->eng->poaMu);
@@ -2105,6 +2196,33 @@ int pbccs_poa_consensus(pbccs_engine* eng, const char* const* reads, const int* 
             if (rc != PBCCS_OK) return rc;
         }
         return put_text(g.Sequence(path), out, cap, len);
+    });
+}
+
+int pbccs_poa_band_stats_get(pbccs_engine* eng, pbccs_poa_band_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->poaMu);
+        poa::BandStats s;
+        for (poa::PoaRunner* r : eng->PoaRunners()) {   // everything adds up over the slices
+            const poa::BandStats& x = r->band;
+            s.bandedAlignments += x.bandedAlignments;
+            s.fallbacks += x.fallbacks;
+            s.bandCells += x.bandCells;
+            s.fullCells += x.fullCells;
+            s.seeds += x.seeds;
+            s.anchors += x.anchors;
+            s.seedMs += x.seedMs;
+            s.rangesMs += x.rangesMs;
+            s.fillMs += x.fillMs;
+            s.traceMs += x.traceMs;
+            s.scoreBytes += x.scoreBytes;
+            if (reset) r->band = poa::BandStats();
+        }
+        *out = pbccs_poa_band_stats{s.bandedAlignments, s.fallbacks, s.bandCells, s.fullCells, s.seeds,     s.anchors,
+                                    s.seedMs,           s.rangesMs,  s.fillMs,    s.traceMs,   s.scoreBytes};
+        return PBCCS_OK;
     });
 }
 
@@ -2341,7 +2459,7 @@ static void bind_polish_outputs(CcsChunk* C, const pbccs_ccs_output* out)
 // (key -2) are placed on the finished drafts and treated like POA reads: one MapRunner call per POA slice, on the
 // slice's thread once its drafts are final, while the other slices' POA rounds go on.
 static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const pbccs_polish_options& o,
-                            long long max_poa_coverage, bool mapPastCap,
+                            long long max_poa_coverage, bool mapPastCap, bool bandedPoa,
                             const std::vector<std::vector<driver::Subread>>& sub,
                             const std::vector<std::vector<int>>& order, pbccs_ccs_output* out, CcsChunk* C)
 {
@@ -2389,7 +2507,7 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
             if (r.status != PBCCS_OK) throw DeviceOom("a read's boundary buffers exceed the map workspace");
     };
     poa::PoaBatch(eng->PoaRunners(), poaReads, max_poa_coverage, -1, &C->css, &keys, &rc, &ext,
-                  mapPastCap ? &mapSlice : nullptr);
+                  mapPastCap ? &mapSlice : nullptr, bandedPoa);
     C->mapped.resize(m);
     C->seqPtr.resize(m);
     C->lens.resize(m);
@@ -2459,7 +2577,7 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
 }
 
 static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
-                          bool mapPastCap, const pbccs_polish_options* opts, pbccs_ccs_output* out)
+                          bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
     pbccs_polish_options o;
@@ -2620,7 +2738,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             }
             const double d0 = since();
             try {
-                ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, sub, order, out, &chunks[c]);
+                ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, bandedPoa, sub, order, out, &chunks[c]);
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d draft zmws %zu %.1f-%.1f ms\n", c, chunks[c].zs.size(), d0,
                                  since());
@@ -2707,7 +2825,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
 int pbccs_ccs_batch(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
                     const pbccs_polish_options* opts, pbccs_ccs_output* out)
 {
-    return ccs_batch_impl(eng, in, n, max_poa_coverage, false, opts, out);
+    return ccs_batch_impl(eng, in, n, max_poa_coverage, false, false, opts, out);
 }
 
 void pbccs_ccs_options_default(pbccs_ccs_options* o)
@@ -2723,7 +2841,16 @@ int pbccs_ccs_batch_ex(pbccs_engine* eng, const pbccs_ccs_input* in, int n, cons
     pbccs_ccs_options c;
     if (ccs) c = *ccs;
     else pbccs_ccs_options_default(&c);
-    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, opts, out);
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, false, opts, out);
+}
+
+int pbccs_ccs_batch_ex2(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_polish_options* opts, pbccs_ccs_output* out)
+{
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out);
 }
 
 }  // extern "C"

@@ -448,6 +448,486 @@ __global__ __launch_bounds__(64) void k_poa_trace(const PoaJob* __restrict__ job
     heads[t] = TraceHeader{n, prevRow, vtx[ec], 0};
 }
 
+// ---- the banded fill --------------------------------------------------------------------------
+constexpr int kBig = INT_MAX / 2;    // RangeUnion({}) = (kBig, -kBig)
+constexpr int kNoRange = INT_MIN;    // a column without a direct range
+constexpr int kBandWidth = sparse::kWidth;
+
+// SdpRangeFinder::InitRangeFinder (RangeFinder.cpp:71-165) over the column program, one wavefront per alignment.
+// The direct ranges are written by all lanes (a chain's anchors rise strictly in h, so no two name one column).
+// The two recursions are chains over the topological order: forwards each column pulls next(fwd(pred), I) from its
+// predecessor list; backwards each column, final once every later column has run, pushes prev(rev, 0) into its
+// predecessors -- $ first, whose rev is RangeUnion({}).  The backward pass also lays the columns' bands out in the
+// score arena (cellOff) and totals them.
+// Both run on the whole wave with uniform control flow, 64 columns at a time: a lane loads one column's direct
+// range, predecessor list and first predecessor, the chain takes them with readlane, and a column's result goes
+// into its lane's registers -- where a predecessor (forwards) or a push (backwards) inside the block finds it -- and
+// to memory once per block.  Only a predecessor in another block costs a load on the chain.
+__global__ __launch_bounds__(64) void k_poa_ranges(const BandJob* __restrict__ band, PoaPools P,
+                                                   const int* __restrict__ anchors, const int* __restrict__ cssCol,
+                                                   int* range, int* fwd, int* acc, long long* cellOff, long long* cells)
+{
+    const BandJob B = band[blockIdx.x];
+    const int lane = threadIdx.x;
+    int* rg = range + 2 * B.colOff;
+    int* fw = fwd + 2 * B.colOff;
+    int* ac = acc + 2 * B.colOff;
+    long long* co = cellOff + B.colOff;
+    const int I = B.I, nC = B.nCols;
+    for (int c = lane; c < nC; c += 64) {
+        rg[2 * c] = kNoRange;
+        rg[2 * c + 1] = 0;
+        ac[2 * c] = kBig;
+        ac[2 * c + 1] = -kBig;
+    }
+    __syncthreads();
+    const int* a = anchors + 2 * B.anchorOff;
+    const int* cc = cssCol + B.cssOff;
+    for (int x = lane; x < B.nAnchors; x += 64) {
+        const int h = a[2 * x], v = a[2 * x + 1];
+        if ((unsigned)h >= (unsigned)B.cssLen) continue;   // cannot happen: h <= cssLen - K
+        const int c = cc[h];
+        if ((unsigned)c >= (unsigned)nC) continue;
+        rg[2 * c] = max(v - kBandWidth, 0);
+        rg[2 * c + 1] = min(v + kBandWidth, I);
+    }
+    // $'s predecessors (distinct columns) take prev(RangeUnion({}), 0)
+    for (int x = lane; x < B.nExit; x += 64) {
+        const int u = P.exitPred[B.exitOff + x];
+        ac[2 * u] = max(kBig - 1, 0);
+        ac[2 * u + 1] = max(-kBig - 1, 0);
+    }
+    __syncthreads();
+    const int* ps = P.predStart + B.predStartOff;
+    // ---- forwards
+    for (int kb = 0; kb < nC; kb += 64) {
+        const int c = kb + lane;
+        const bool in = c < nC;
+        int dB = kNoRange, dE = 0, mPs = 0, mPe = 0, mU0 = -1;
+        if (in) {
+            dB = rg[2 * c], dE = rg[2 * c + 1];
+            mPs = ps[c], mPe = ps[c + 1];
+            if (mPe > mPs) mU0 = P.predCol[mPs];
+        }
+        int myB = 0, myE = 0;   // fwd of this lane's column, once the chain has passed it
+        const int kend = min(64, nC - kb);
+        for (int x = 0; x < kend; ++x) {
+            int b = __builtin_amdgcn_readlane(dB, x), e = __builtin_amdgcn_readlane(dE, x);
+            if (b == kNoRange) {
+                b = kBig, e = -kBig;
+                const int p0 = __builtin_amdgcn_readlane(mPs, x), p1 = __builtin_amdgcn_readlane(mPe, x);
+                for (int p = p0; p < p1; ++p) {
+                    const int u = p == p0 ? __builtin_amdgcn_readlane(mU0, x) : P.predCol[p];
+                    int ub, ue;
+                    if (u >= kb) {
+                        ub = __builtin_amdgcn_readlane(myB, u - kb), ue = __builtin_amdgcn_readlane(myE, u - kb);
+                    } else {   // an earlier block's, stored and fenced below
+                        ub = fw[2 * u], ue = fw[2 * u + 1];
+                    }
+                    b = min(b, min(ub + 1, I));
+                    e = max(e, min(ue + 1, I));
+                }
+            }
+            if (lane == x) myB = b, myE = e;
+        }
+        if (in) {
+            fw[2 * c] = myB;
+            fw[2 * c + 1] = myE;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // other lanes load them in later blocks
+    }
+    // ---- backwards
+    long long total = 0;
+    for (int kb = (nC - 1) / 64 * 64; kb >= 0; kb -= 64) {
+        const int c = kb + lane;
+        const bool in = c < nC;
+        int dB = kNoRange, dE = 0, aB = kBig, aE = -kBig, fB = 0, fE = 0, mPs = 0, mPe = 0, mU0 = -1;
+        if (in) {
+            dB = rg[2 * c], dE = rg[2 * c + 1];
+            aB = ac[2 * c], aE = ac[2 * c + 1];   // what $ and the later blocks pushed
+            fB = fw[2 * c], fE = fw[2 * c + 1];
+            mPs = ps[c], mPe = ps[c + 1];
+            if (mPe > mPs) mU0 = P.predCol[mPs];
+        }
+        int outB = 0, outE = 0, outLo = 0, outHi = 0;
+        const int kend = min(64, nC - kb);
+        for (int x = kend - 1; x >= 0; --x) {
+            const int db = __builtin_amdgcn_readlane(dB, x);
+            const bool direct = db != kNoRange;
+            const int b = direct ? db : __builtin_amdgcn_readlane(aB, x);
+            const int e = direct ? __builtin_amdgcn_readlane(dE, x) : __builtin_amdgcn_readlane(aE, x);
+            const int pb = max(b - 1, 0), pe = max(e - 1, 0);
+            const int p0 = __builtin_amdgcn_readlane(mPs, x), p1 = __builtin_amdgcn_readlane(mPe, x);
+            for (int p = p0; p < p1; ++p) {
+                const int u = p == p0 ? __builtin_amdgcn_readlane(mU0, x) : P.predCol[p];
+                if (u >= kb) {
+                    if (lane == u - kb) aB = min(aB, pb), aE = max(aE, pe);
+                } else if (lane == 0) {   // an earlier block's column: it loads what is pushed here, after the fence
+                    ac[2 * u] = min(ac[2 * u], pb);
+                    ac[2 * u + 1] = max(ac[2 * u + 1], pe);
+                }
+            }
+            const int hb = min(__builtin_amdgcn_readlane(fB, x), b), he = max(__builtin_amdgcn_readlane(fE, x), e);
+            const int hi = min(he, I);
+            if (lane == x) {
+                outB = hb, outE = he;
+                outLo = (int)(total & 0xFFFFFFFFLL), outHi = (int)(total >> 32);
+            }
+            total += hi >= hb ? hi - hb + 1 : 0;
+        }
+        if (in) {
+            rg[2 * c] = outB;
+            rg[2 * c + 1] = outE;
+            co[c] = ((long long)outHi << 32) | (unsigned)outLo;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    }
+    if (lane == 0) cells[blockIdx.x] = total;
+}
+
+// The rows a column holds under its range [B, E): B <= i <= min(E, I) (closed above, so row I exists when E == I).
+struct BandCol {
+    int lo, len;
+    __device__ __forceinline__ BandCol(const int* rg, int c, int I)
+    {
+        lo = rg[2 * c];
+        const int hi = min(rg[2 * c + 1], I);
+        len = hi >= lo ? hi - lo + 1 : 0;
+    }
+    __device__ __forceinline__ bool has(int i) const { return i >= lo && i - lo < len; }
+};
+
+// TryAddRead's columns inside their bands (LOCAL).  One wavefront per alignment, a lane per row of the band, 64
+// rows per pass; a column's scores lie at cellOff[column] + (row - B).  A cell outside its column's band offers no
+// candidate; every cell starts from LOCAL's 0.  The Extra move is the prefix maximum of k_poa_fill, taken over the
+// band's rows only (the pass's lanes past the band hold kNeg), with the carry between passes.
+//
+// A column is a handful of rows, so the time is the chain of loads in front of them.  Three things keep it short:
+//   * the column program is read 64 columns at a time, one column per lane (band, arena offset, predecessor list,
+//     first predecessor, base, vertex), and handed to the column loop with readlane; the block before stays in
+//     registers for predecessors that lie in it, an older predecessor's band is read from memory;
+//   * the last kBandRing columns' scores stay in an LDS ring (bands of up to kBandSlot rows), so the usual
+//     predecessor -- the column before -- is an LDS read, and the workgroup fence that makes the wave's global
+//     stores visible to its own loads is paid only for a predecessor outside the ring;
+//   * the read's bases are staged in LDS (ldsRead bytes of it; a longer read stays in memory).
+constexpr int kBandRing = 8;
+constexpr int kBandSlot = 256;
+constexpr int kBandT = 4;             // 64-row passes taken together: a ring slot's rows
+constexpr int kBandWideRows = 8;      // rows a lane of a band past a ring slot
+constexpr int kBandReadLds = 32 * 1024;
+
+template <class ST>
+__global__ __launch_bounds__(64) void k_poa_fill_band(const PoaJob* __restrict__ jobs, const int* __restrict__ bandOf,
+                                                      const BandJob* __restrict__ band, int jobBase, PoaPools P,
+                                                      const int* __restrict__ range,
+                                                      const long long* __restrict__ cellOff, ST* pool,
+                                                      int* __restrict__ outScore, int* __restrict__ outExitCol,
+                                                      int ldsRead)
+{
+    extern __shared__ __align__(16) unsigned char bandLds[];
+    ST* ring = reinterpret_cast<ST*>(bandLds);                                // kBandRing x kBandSlot
+    uint8_t* rdL = bandLds + kBandRing * kBandSlot * (int)sizeof(ST);          // rows 0..I of the read
+    const int j = jobBase + blockIdx.x;
+    const PoaJob J = jobs[j];
+    const BandJob B = band[bandOf[j]];
+    const int lane = threadIdx.x;
+    ST* S = pool + J.scoreOff;
+    const uint8_t* rb = P.rowBase + J.readOff;
+    const int* rg = range + 2 * B.colOff;
+    const long long* co = cellOff + B.colOff;
+    const int I = J.I, nC = J.nCols;
+    const int* predStart = P.predStart + J.predStartOff;
+    const bool readInLds = I + 1 <= ldsRead;
+    if (readInLds)
+        for (int i = lane; i <= I; i += 64) rdL[i] = rb[i];
+    __syncthreads();
+    bool dirty = false;
+    int bestVal = kNeg, bestVid = INT_MAX, bestCol = 0;
+    // this block's columns (m*) and the block before (q*), one column per lane
+    int mLo = 0, mLen = 0, mOffLo = 0, mOffHi = 0, qLo = 0, qLen = 0, qOffLo = 0, qOffHi = 0;
+    for (int kb = 0; kb < nC; kb += 64) {
+        qLo = mLo, qLen = mLen, qOffLo = mOffLo, qOffHi = mOffHi;
+        const int c = kb + lane;
+        const bool in = c < nC;
+        int mPs = 0, mPe = 0, mBase = 0, mVid = 0, mU0 = -1;
+        mLo = mLen = mOffLo = mOffHi = 0;
+        if (in) {
+            const BandCol C(rg, c, I);
+            const long long o = co[c];
+            mLo = C.lo, mLen = C.len, mOffLo = (int)(o & 0xFFFFFFFFLL), mOffHi = (int)(o >> 32);
+            mPs = predStart[c], mPe = predStart[c + 1];
+            mBase = P.base[J.progOff + c];
+            mVid = P.vertexOfCol[J.progOff + c];
+            if (mPe > mPs) mU0 = P.predCol[mPs];
+        }
+        // a predecessor's band: from this block's registers, the block before's, or memory
+        auto predBand = [&](int u, int& ulo, int& ulen, long long& uoff) {
+            if (u >= kb) {
+                const int l = u - kb;
+                ulo = __builtin_amdgcn_readlane(mLo, l), ulen = __builtin_amdgcn_readlane(mLen, l);
+                uoff = ((long long)__builtin_amdgcn_readlane(mOffHi, l) << 32) |
+                       (unsigned)__builtin_amdgcn_readlane(mOffLo, l);
+            } else if (u >= kb - 64) {
+                const int l = u - (kb - 64);
+                ulo = __builtin_amdgcn_readlane(qLo, l), ulen = __builtin_amdgcn_readlane(qLen, l);
+                uoff = ((long long)__builtin_amdgcn_readlane(qOffHi, l) << 32) |
+                       (unsigned)__builtin_amdgcn_readlane(qOffLo, l);
+            } else {
+                const BandCol U(rg, u, I);
+                ulo = U.lo, ulen = U.len, uoff = co[u];
+            }
+        };
+        const int kend = min(64, nC - kb);
+        for (int x = 0; x < kend; ++x) {
+            const int k = kb + x;
+            const int len = __builtin_amdgcn_readlane(mLen, x);
+            if (len == 0) continue;   // an empty column offers nothing
+            const int lo = __builtin_amdgcn_readlane(mLo, x);
+            const long long off = ((long long)__builtin_amdgcn_readlane(mOffHi, x) << 32) |
+                                  (unsigned)__builtin_amdgcn_readlane(mOffLo, x);
+            const int ps = __builtin_amdgcn_readlane(mPs, x), pe = __builtin_amdgcn_readlane(mPe, x);
+            const int base = __builtin_amdgcn_readlane(mBase, x), vid = __builtin_amdgcn_readlane(mVid, x);
+            const int u0 = __builtin_amdgcn_readlane(mU0, x);
+            const bool ringed = len <= kBandSlot;
+            ST* slot = ring + (k % kBandRing) * kBandSlot;
+            ST* col = S + off;
+            int carry = kNeg, colBest = kNeg;
+            // A band past a ring slot (a hull of marks from anchors on distant diagonals: the wrong strand's stray
+            // anchors make them) is filled as k_poa_fill fills a column: kBandWideRows consecutive rows a lane, their
+            // Extra terms taken in the lane, then across the wave.  It lives in memory only.
+            for (int c0 = 0; !ringed && c0 < len; c0 += 64 * kBandWideRows) {
+                const int r0 = c0 + lane * kBandWideRows, i0 = lo + r0;
+                int ne[kBandWideRows], sub[kBandWideRows];
+#pragma unroll
+                for (int t = 0; t < kBandWideRows; ++t) {
+                    const bool valid = r0 + t < len;
+                    ne[t] = valid ? 0 : kNeg;   // Start
+                    int rbase = -1;
+                    if (valid && i0 + t > 0) rbase = readInLds ? rdL[i0 + t] : rb[i0 + t];
+                    sub[t] = rbase == base ? kMatchScore : kMismatchScore;
+                }
+                for (int p = ps; p < pe; ++p) {
+                    const int u = p == ps ? u0 : P.predCol[p];
+                    int ulo, ulen;
+                    long long uoff;
+                    predBand(u, ulo, ulen, uoff);
+                    if (ulen == 0) continue;
+                    // rows i0 - 1 .. i0 + kBandWideRows - 1 of the predecessor; a cell that does not exist reads kNeg,
+                    // which loses to the Start every valid row holds
+                    auto absorb = [&](auto q) {
+                        const int x0 = i0 - 1 - ulo;
+                        int up = (x0 >= 0 && x0 < ulen) ? (int)q[x0] : kNeg;
+#pragma unroll
+                        for (int t = 0; t < kBandWideRows; ++t) {
+                            const int xt = x0 + 1 + t;
+                            const int at = (xt >= 0 && xt < ulen) ? (int)q[xt] : kNeg;
+                            ne[t] = max(ne[t], max(up + sub[t], at + kDeleteScore));
+                            up = at;
+                        }
+                    };
+                    if (k - u < kBandRing && ulen <= kBandSlot) {
+                        absorb((const ST*)(ring + (u % kBandRing) * kBandSlot));
+                    } else {
+                        if (dirty) {
+                            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                            dirty = false;
+                        }
+                        absorb((const ST*)(S + uoff));
+                    }
+                }
+                int run = kNeg;
+#pragma unroll
+                for (int t = 0; t < kBandWideRows; ++t) {
+                    if (r0 + t < len) run = max(run, ne[t] - (i0 + t) * kInsertScore);
+                    ne[t] = run;
+                }
+                const int incl = wave_prefix_max(run);
+                const int excl = max(dpp_i<0x138, 0xF>(kNeg, incl), carry);   // wave_shr:1
+#pragma unroll
+                for (int t = 0; t < kBandWideRows; ++t) {
+                    const int v = max(ne[t], excl) + (i0 + t) * kInsertScore;
+                    if (r0 + t < len) {
+                        col[r0 + t] = (ST)v;
+                        colBest = max(colBest, v);
+                    }
+                }
+                carry = __builtin_amdgcn_readlane(max(incl, carry), 63);
+            }
+            // kBandT passes' rows at a time: their predecessor cells are loaded together, the prefix maxima follow
+            // pass by pass with the carry
+            for (int c0 = 0; ringed && c0 < len; c0 += 64 * kBandT) {
+                int ne[kBandT], sub[kBandT];
+#pragma unroll
+                for (int t = 0; t < kBandT; ++t) {
+                    const int r = c0 + 64 * t + lane, i = lo + r;
+                    const bool valid = r < len;
+                    ne[t] = valid ? 0 : kNeg;   // Start; row 0 is 0 by it
+                    int rbase = -1;
+                    if (valid && i > 0) rbase = readInLds ? rdL[i] : rb[i];
+                    sub[t] = rbase == base ? kMatchScore : kMismatchScore;
+                }
+                for (int p = ps; p < pe; ++p) {
+                    const int u = p == ps ? u0 : P.predCol[p];
+                    int ulo, ulen;
+                    long long uoff;
+                    predBand(u, ulo, ulen, uoff);
+                    if (ulen == 0) continue;
+                    if (k - u < kBandRing && ulen <= kBandSlot) {
+                        const ST* q = ring + (u % kBandRing) * kBandSlot;
+#pragma unroll
+                        for (int t = 0; t < kBandT; ++t) {
+                            const int r = c0 + 64 * t + lane, i = lo + r;
+                            const bool valid = r < len;
+                            if (valid && i > 0 && i - 1 >= ulo && i - 1 - ulo < ulen)
+                                ne[t] = max(ne[t], (int)q[i - 1 - ulo] + sub[t]);
+                            if (valid && i >= ulo && i - ulo < ulen) ne[t] = max(ne[t], (int)q[i - ulo] + kDeleteScore);
+                        }
+                    } else {
+                        if (dirty) {   // the wave's own stores, made visible to its loads
+                            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                            dirty = false;
+                        }
+                        const ST* q = S + uoff;
+#pragma unroll
+                        for (int t = 0; t < kBandT; ++t) {
+                            const int r = c0 + 64 * t + lane, i = lo + r;
+                            const bool valid = r < len;
+                            if (valid && i > 0 && i - 1 >= ulo && i - 1 - ulo < ulen)
+                                ne[t] = max(ne[t], (int)q[i - 1 - ulo] + sub[t]);
+                            if (valid && i >= ulo && i - ulo < ulen) ne[t] = max(ne[t], (int)q[i - ulo] + kDeleteScore);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < kBandT; ++t) {
+                    if (c0 + 64 * t >= len) break;
+                    const int r = c0 + 64 * t + lane, i = lo + r;
+                    const bool valid = r < len;
+                    const int g = valid ? ne[t] - i * kInsertScore : kNeg;
+                    const int incl = max(wave_prefix_max(g), carry);
+                    const int v = incl + i * kInsertScore;
+                    if (valid) {
+                        col[r] = (ST)v;
+                        if (ringed) slot[r] = (ST)v;
+                        colBest = max(colBest, v);
+                    }
+                    carry = __builtin_amdgcn_readlane(incl, 63);
+                }
+            }
+            dirty = true;
+            if (colBest > bestVal || (colBest == bestVal && vid < bestVid)) {
+                bestVal = colBest;
+                bestVid = vid;
+                bestCol = k;
+            }
+            // The ring is read and written by this one wavefront, whose LDS instructions execute in order: a later
+            // column's reads follow this column's writes without a barrier (which would also wait for the global
+            // stores).  Only the compiler has to keep the order.
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    int key = bestVid;
+    const int v0 = bestVal;
+    wave_argmax(bestVal, key);
+    const unsigned long long m = __ballot(v0 == bestVal && bestVid == key);
+    bestCol = __shfl(bestCol, (int)__builtin_ctzll(m));
+    if (lane == 0) {
+        outScore[j] = bestVal;
+        outExitCol[j] = bestCol;
+    }
+}
+
+// k_poa_trace over banded scores: the same candidate order and strict '>', a cell outside its column's band
+// offering nothing.  The walk only ever stands on a cell that exists (the exit column's first maximal existing row,
+// then cells that offered a candidate).
+template <class ST>
+__global__ __launch_bounds__(64) void k_poa_trace_band(const PoaJob* __restrict__ jobs, const int* __restrict__ bandOf,
+                                                       const BandJob* __restrict__ band,
+                                                       const int* __restrict__ traceJobs, int traceBase, PoaPools P,
+                                                       const int* __restrict__ range,
+                                                       const long long* __restrict__ cellOff,
+                                                       const ST* __restrict__ pool, const int* __restrict__ exitCol,
+                                                       uint32_t* __restrict__ steps, TraceHeader* __restrict__ heads)
+{
+    const int t = traceBase + blockIdx.x;
+    const int j = traceJobs[t];
+    const PoaJob J = jobs[j];
+    const BandJob B = band[bandOf[j]];
+    const int lane = threadIdx.x;
+    const ST* S = pool + J.scoreOff;
+    const int* rg = range + 2 * B.colOff;
+    const long long* co = cellOff + B.colOff;
+    const int I = J.I;
+    const int ec = exitCol[j];
+    const int* vtx = P.vertexOfCol + J.progOff;
+    const int* predStart = P.predStart + J.predStartOff;
+    const uint8_t* baseT = P.base + J.progOff;
+    // the End move comes from the first maximal existing row of the exit's column
+    const BandCol E(rg, ec, I);
+    int bv = kNeg, br = INT_MAX;
+    for (int r = lane; r < E.len; r += 64) {
+        const int v = (int)S[co[ec] + r];
+        if (v > bv) {
+            bv = v;
+            br = E.lo + r;
+        }
+    }
+    wave_argmax(bv, br);
+    const int prevRow = br;
+    if (lane != 0) return;
+    uint32_t* out = steps + J.stepOff;
+    const int cap = I + J.nCols + 2;
+    int n = 0;
+    out[n++] = pack_step(kExit, kEnd);
+    int k = ec, i = prevRow;
+    const uint8_t* rb = P.rowBase + J.readOff;
+    if (E.len == 0) n = -1;   // cannot happen: the exit names a column that offered a score
+    while (n > 0 && !(k == 0 && i == 0)) {
+        if (n >= cap) {
+            n = -1;
+            break;
+        }
+        int mv = kStart, pv = 0;
+        if (i > 0) {
+            int best = 0;
+            const bool isMatch = rb[i] == baseT[k];
+            for (int p = predStart[k]; p < predStart[k + 1]; ++p) {
+                const int c = P.predCol[p];
+                const BandCol U(rg, c, I);
+                if (U.has(i - 1)) {
+                    const int cand = (int)S[co[c] + (i - 1 - U.lo)] + (isMatch ? kMatchScore : kMismatchScore);
+                    if (cand > best) {
+                        best = cand;
+                        pv = c;
+                        mv = isMatch ? kMatch : kMismatch;
+                    }
+                }
+                if (U.has(i)) {
+                    const int cand = (int)S[co[c] + (i - U.lo)] + kDeleteScore;
+                    if (cand > best) {
+                        best = cand;
+                        pv = c;
+                        mv = kDelete;
+                    }
+                }
+            }
+            const BandCol C(rg, k, I);
+            if (C.has(i - 1)) {
+                const int cand = (int)S[co[k] + (i - 1 - C.lo)] + kInsertScore;
+                if (cand > best) {
+                    pv = k;
+                    mv = kExtra;
+                }
+            }
+        }
+        out[n++] = pack_step(vtx[k], mv);
+        if (mv == kStart) i = 0;
+        else if (mv != kDelete) i--;
+        k = pv;
+    }
+    heads[t] = TraceHeader{n, prevRow, vtx[ec], 0};
+}
+
 // ConsensusCore Sequence.cpp:44-105 (ComplementArray; note N <-> M)
 char complement(char c)
 {
@@ -487,6 +967,7 @@ int variant_stride(int variant, int rows)
     return variant == 0 ? (rows + kChunkRows - 1) / kChunkRows * kChunkRows : 64 * rows_per_lane(variant, rows);
 }
 constexpr int kRing = 4;   // columns kept in LDS by the ring variants
+constexpr int kBandVariant = kRingVariants + 1;   // k_poa_fill_band: scores laid out band by band
 
 template <class ST>
 void launch_fill(int variant, int n, int base, hipStream_t s, const PoaJob* jobs, const PoaPools& P, ST* pool,
@@ -543,6 +1024,7 @@ PoaRunner::PoaRunner(int device, int hostThreads) : device_(device)
     check(hipSetDevice(device_), "hipSetDevice");
     check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
     for (auto& e : ev_) check(hipEventCreate(&e), "hipEventCreate");
+    for (auto& e : bev_) check(hipEventCreate(&e), "hipEventCreate");
     dPool_.allowVmm = true;
 }
 
@@ -550,9 +1032,132 @@ PoaRunner::~PoaRunner()
 {
     (void)hipSetDevice(device_);
     if (stream_) (void)hipStreamSynchronize(stream_);
+    seeder_.reset();   // it runs on stream_
     for (auto& e : ev_)
         if (e) (void)hipEventDestroy(e);
+    for (auto& e : bev_)
+        if (e) (void)hipEventDestroy(e);
     if (stream_) (void)hipStreamDestroy(stream_);
+}
+
+void PoaRunner::SeedAndRange(const std::vector<BandJob>& geom, const std::vector<const std::string*>& css,
+                             const std::vector<const std::string*>& read, const std::vector<int>& rc,
+                             const std::vector<const std::vector<int>*>& cssCol, const PoaPools& pools,
+                             std::vector<long long>* cells, std::vector<sparse::KeptChain>* chains)
+{
+    const int nb = (int)geom.size();
+    cells->assign(nb, -1);
+    chains->assign(nb, sparse::KeptChain());
+    if (nb == 0) return;
+    if (!seeder_) seeder_.reset(new sparse::SparseRunner(device_, stream_));
+    seeder_->profiling = profiling;
+    // rule 2: SparseAlign<6>(css, read); the reverse complement is formed on the device
+    std::vector<sparse::SparseInput> in(nb);
+    for (int b = 0; b < nb; ++b)
+        in[b] = sparse::SparseInput{css[b]->data(), (int)css[b]->size(), read[b]->data(), (int)read[b]->size(), rc[b],
+                                    nullptr, 0, nullptr};
+    const sparse::SparseStats before = seeder_->stats;
+    seeder_->RunKeep(kBandK, in.data(), nb, chains);
+    band.seeds += seeder_->stats.seeds - before.seeds;
+    band.seedMs += seeder_->stats.deviceMs - before.deviceMs;
+    // rule 5: no anchors (which covers a sequence shorter than K), a letter outside ACGT, or the seeding out of memory
+    std::vector<BandJob> live;
+    std::vector<int> liveOf;
+    std::vector<int> hCss;
+    long long cols = 0;
+    for (int b = 0; b < nb; ++b) {
+        const sparse::KeptChain& c = (*chains)[b];
+        if (c.status != 0 || c.nAnchors <= 0) continue;
+        BandJob B = geom[b];
+        B.anchorOff = c.anchorOff;
+        B.nAnchors = c.nAnchors;
+        B.cssOff = (long long)hCss.size();
+        B.cssLen = (int)cssCol[b]->size();
+        B.colOff = cols;
+        hCss.insert(hCss.end(), cssCol[b]->begin(), cssCol[b]->end());
+        cols += B.nCols;
+        live.push_back(B);
+        liveOf.push_back(b);
+        band.anchors += c.nAnchors;
+    }
+    const int nl = (int)live.size();
+    if (nl == 0) return;
+    dBand_.reserve(nl, false);
+    dCssCol_.reserve(std::max<size_t>(1, hCss.size()), false);
+    dRange_.reserve(2 * (size_t)cols, false);
+    dFwd_.reserve(2 * (size_t)cols, false);
+    dAcc_.reserve(2 * (size_t)cols, false);
+    dCellOff_.reserve((size_t)cols, false);
+    dCells_.reserve(nl, false);
+    // pageable sources: the copies are staged before the calls return
+    check(hipMemcpyAsync(dBand_.ptr, live.data(), nl * sizeof(BandJob), hipMemcpyHostToDevice, stream_), "upload");
+    check(hipMemcpyAsync(dCssCol_.ptr, hCss.data(), hCss.size() * sizeof(int), hipMemcpyHostToDevice, stream_), "upload");
+    if (profiling) check(hipEventRecord(bev_[0], stream_), "event");
+    hipLaunchKernelGGL(k_poa_ranges, dim3(nl), dim3(64), 0, stream_, dBand_.ptr, pools, seeder_->AnchorsDevice(),
+                       dCssCol_.ptr, dRange_.ptr, dFwd_.ptr, dAcc_.ptr, dCellOff_.ptr, dCells_.ptr);
+    check(hipGetLastError(), "k_poa_ranges launch");
+    stats.launches++;
+    if (profiling) check(hipEventRecord(bev_[1], stream_), "event");
+    std::vector<long long> hCells(nl);
+    check(hipMemcpyAsync(hCells.data(), dCells_.ptr, nl * sizeof(long long), hipMemcpyDeviceToHost, stream_), "d2h");
+    check(hipStreamSynchronize(stream_), "k_poa_ranges");
+    if (profiling) {
+        float ms = 0.f;
+        check(hipEventElapsedTime(&ms, bev_[0], bev_[1]), "event");
+        band.rangesMs += ms;
+    }
+    for (int x = 0; x < nl; ++x) {
+        (*cells)[liveOf[x]] = hCells[x];
+        (*chains)[liveOf[x]].anchorOff = x;   // from here on: the alignment's place in the device's BandJob array
+    }
+}
+
+void PoaRunner::Ranges(PoaGraph* graph, const std::string& read, bool rc, RangeReport* out)
+{
+    check(hipSetDevice(device_), "hipSetDevice");
+    const StreamScope bound(stream_);
+    *out = RangeReport();
+    ColumnProgram C;
+    graph->Program(&C);
+    out->cssPath = graph->ConsensusPath(kLocal, -INT_MAX, C);
+    const std::string css = graph->Sequence(out->cssPath);
+    std::vector<int> cssCol;
+    for (int v : out->cssPath) cssCol.push_back(C.colOfVertex[v]);
+    const int nCols = (int)C.vertexOfCol.size();
+    dPredStart_.reserve(nCols + 1, false);
+    dPredCol_.reserve(std::max<size_t>(1, C.predCol.size()), false);
+    dExitPred_.reserve(std::max<size_t>(1, C.exitPredCol.size()), false);
+    check(hipMemcpyAsync(dPredStart_.ptr, C.predStart.data(), (nCols + 1) * sizeof(int), hipMemcpyHostToDevice, stream_),
+          "upload");
+    if (!C.predCol.empty())
+        check(hipMemcpyAsync(dPredCol_.ptr, C.predCol.data(), C.predCol.size() * sizeof(int), hipMemcpyHostToDevice,
+                             stream_), "upload");
+    if (!C.exitPredCol.empty())
+        check(hipMemcpyAsync(dExitPred_.ptr, C.exitPredCol.data(), C.exitPredCol.size() * sizeof(int),
+                             hipMemcpyHostToDevice, stream_), "upload");
+    const PoaPools pools{nullptr, nullptr, dPredStart_.ptr, dPredCol_.ptr, dExitPred_.ptr, nullptr};
+    BandJob B{};
+    B.nCols = nCols;
+    B.I = (int)read.size();
+    B.nExit = (int)C.exitPredCol.size();
+    std::vector<long long> cells;
+    std::vector<sparse::KeptChain> chains;
+    SeedAndRange({B}, {&css}, {&read}, {rc ? 1 : 0}, {&cssCol}, pools, &cells, &chains);
+    out->status = chains[0].status;
+    if (cells[0] < 0) return;
+    // this entry point hands anchors and ranges to the host; the fill never does
+    std::vector<BandJob> hb(1);
+    check(hipMemcpy(hb.data(), dBand_.ptr, sizeof(BandJob), hipMemcpyDeviceToHost), "d2h");
+    out->anchors.resize(2 * (size_t)chains[0].nAnchors);
+    check(hipMemcpy(out->anchors.data(), seeder_->AnchorsDevice() + 2 * hb[0].anchorOff,
+                    out->anchors.size() * sizeof(int), hipMemcpyDeviceToHost), "d2h");
+    std::vector<int> rg(2 * (size_t)nCols);
+    check(hipMemcpy(rg.data(), dRange_.ptr, rg.size() * sizeof(int), hipMemcpyDeviceToHost), "d2h");
+    out->ranges.assign(2 * graph->NumVertices(), 0);
+    for (int c = 0; c < nCols; ++c) {
+        out->ranges[2 * C.vertexOfCol[c]] = rg[2 * c];
+        out->ranges[2 * C.vertexOfCol[c] + 1] = rg[2 * c + 1];
+    }
 }
 
 void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>* out)
@@ -568,12 +1173,26 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
     if ((int)prog_.size() < n) prog_.resize(n);
     std::vector<ColumnProgram>& prog = prog_;
     std::vector<std::string> rcRead(n);
+    // banded requests (LOCAL): rule 1's consensus path, as its sequence and as columns of the program
+    std::vector<char> wantBand(n, 0);
+    std::vector<std::string> cssSeq(n);
+    std::vector<std::vector<int>> cssCol(n);
     ParallelFor(n, [&](int r) {
         reqs[r].graph->Program(&prog[r]);
         if (reqs[r].orient) rcRead[r] = reverse_complement(reqs[r].read);
+        wantBand[r] = reqs[r].banded && reqs[r].mode == kLocal && reqs[r].graph->NumReads() > 0;
+        if (wantBand[r]) {
+            const std::vector<int> path = reqs[r].graph->ConsensusPath(kLocal, -INT_MAX, prog[r]);
+            cssSeq[r] = reqs[r].graph->Sequence(path);
+            cssCol[r].resize(path.size());
+            for (size_t k = 0; k < path.size(); ++k) cssCol[r][k] = prog[r].colOfVertex[path[k]];
+        }
     });
+    // a request's alignments: both orientations of an orienting request, or the one a TryAddRead names
+    auto nOri = [&](int r) { return reqs[r].orient && reqs[r].tryOnly < 0 ? 2 : 1; };
+    auto oriOf = [&](int r, int o) { return reqs[r].tryOnly >= 0 ? (reqs[r].orient && reqs[r].tryOnly ? 1 : 0) : o; };
     std::vector<int> firstJob(n + 1, 0);
-    for (int r = 0; r < n; ++r) firstJob[r + 1] = firstJob[r] + (reqs[r].orient ? 2 : 1);
+    for (int r = 0; r < n; ++r) firstJob[r + 1] = firstJob[r] + nOri(r);
     const int nJobs = firstJob[n];
     hJobs_.reserve(2 * (size_t)nJobs);   // [0, nJobs): by request; [nJobs, 2 nJobs): a group in launch order
     PoaJob* jobs = hJobs_.ptr;
@@ -582,12 +1201,12 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
     for (int r = 0; r < n; ++r) {
         const ColumnProgram& C = prog[r];
         const int nCols = (int)C.vertexOfCol.size();
-        for (int o = 0; o < (reqs[r].orient ? 2 : 1); ++o) {
+        for (int o = 0; o < nOri(r); ++o) {
             const int j = firstJob[r] + o;
             PoaJob& J = jobs[j];
             J = PoaJob{};
             J.nCols = nCols;
-            J.I = (int)(o ? rcRead[r] : reqs[r].read).size();
+            J.I = (int)reqs[r].read.size();
             J.mode = reqs[r].mode;
             // uint16 holds LOCAL scores (>= 0, at most 3 per row) of every row up to the padded stride
             J.wide = !(J.mode == kLocal && 3LL * (J.I + 1 + kChunkRows) < 65536);
@@ -602,7 +1221,7 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
             J.traceSlot = -1;
             nRow += J.colStride + 16;
             jobReq[j] = r;
-            jobOri[j] = o;
+            jobOri[j] = oriOf(r, o);
         }
         nBase += nCols;
         nPredStart += nCols + 1;
@@ -628,9 +1247,9 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
             memcpy(hPredCol_.ptr + predColOff[r], C.predCol.data(), C.predCol.size() * sizeof(int));
         if (!C.exitPredCol.empty())
             memcpy(hExit_.ptr + J.exitOff, C.exitPredCol.data(), C.exitPredCol.size() * sizeof(int));
-        for (int o = 0; o < (reqs[r].orient ? 2 : 1); ++o) {
+        for (int o = 0; o < nOri(r); ++o) {
             const PoaJob& Jo = jobs[firstJob[r] + o];
-            const std::string& s = o ? rcRead[r] : reqs[r].read;
+            const std::string& s = oriOf(r, o) ? rcRead[r] : reqs[r].read;
             uint8_t* rb = hRowBase_.ptr + Jo.readOff;
             rb[0] = 0;
             memcpy(rb + 1, s.data(), s.size());
@@ -659,7 +1278,49 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
         budget = std::min<size_t>((size_t)(0.6 * (double)fr) + dPool_.mapped_bytes(), budget_ ? budget_ : 64ull << 30);
         budget = std::max<size_t>(budget, 64ull << 20);
     }
-    auto jobBytes = [&](const PoaJob& J) {
+    // ---- banded alignments: seeds, chains and ranges on the device; the host learns each one's band cells
+    std::vector<int> bandOf(nJobs, -1);            // job -> its BandJob on the device
+    std::vector<long long> bandCells(nJobs, 0);
+    {
+        std::vector<BandJob> geom;
+        std::vector<const std::string*> gCss, gRead;
+        std::vector<int> gRc, gJob;
+        std::vector<const std::vector<int>*> gCol;
+        for (int r = 0; r < n; ++r) {
+            if (!wantBand[r]) continue;
+            for (int j = firstJob[r]; j < firstJob[r + 1]; ++j) {
+                const PoaJob& J = jobs[j];
+                BandJob B{};
+                B.nCols = J.nCols, B.I = J.I, B.progOff = J.progOff, B.predStartOff = J.predStartOff;
+                B.exitOff = J.exitOff, B.nExit = J.nExit;
+                geom.push_back(B);
+                gCss.push_back(&cssSeq[r]);
+                gRead.push_back(&reqs[r].read);   // the read as given; orientation 1 sets the seeding's flag
+                gRc.push_back(jobOri[j]);
+                gCol.push_back(&cssCol[r]);
+                gJob.push_back(j);
+            }
+        }
+        std::vector<long long> cells;
+        std::vector<sparse::KeptChain> chains;
+        SeedAndRange(geom, gCss, gRead, gRc, gCol, pools, &cells, &chains);
+        for (size_t b = 0; b < geom.size(); ++b) {
+            const int j = gJob[b];
+            if (cells[b] < 0) {
+                (*out)[jobReq[j]].fellBack[jobOri[j]] = true;
+                band.fallbacks++;
+                continue;
+            }
+            bandOf[j] = (int)chains[b].anchorOff;
+            bandCells[j] = cells[b];
+            jobs[j].variant = kBandVariant;
+            // band scores need no padded stride: uint16 holds every LOCAL score of the read
+            jobs[j].wide = !(3LL * (jobs[j].I + 1) < 65536);
+            jobs[j].rowsPerLane = 0;
+        }
+    }
+    auto jobBytes = [&](const PoaJob& J, int j) {
+        if (J.variant == kBandVariant) return ((size_t)bandCells[j] * (J.wide ? 4 : 2) + 255) / 256 * 256;
         return ((size_t)J.nCols * J.colStride * (J.wide ? 4 : 2) + 255) / 256 * 256;
     };
 
@@ -677,27 +1338,38 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
         int r1 = r0;
         while (r1 < n) {
             size_t b = 0;
-            for (int j = firstJob[r1]; j < firstJob[r1 + 1]; ++j) b += jobBytes(jobs[j]);
+            for (int j = firstJob[r1]; j < firstJob[r1 + 1]; ++j) b += jobBytes(jobs[j], j);
             if (r1 > r0 && bytes + b > budget) break;
             bytes += b;
             r1++;
         }
         const int j0 = firstJob[r0], j1 = firstJob[r1], gn = j1 - j0;
-        // launch order: uint16 jobs, then int32 jobs, each by fill variant (one range per kernel instantiation)
+        // launch order: uint16 jobs, then int32 jobs, each by fill variant (one range per kernel instantiation);
+        // the banded jobs (the last variant) follow their width's full fills
         std::vector<int> order;
         order.reserve(gn);
         for (int w = 0; w < 2; ++w)
-            for (int v = 0; v <= kRingVariants; ++v)
+            for (int v = 0; v <= kBandVariant; ++v)
                 for (int j = j0; j < j1; ++j)
                     if (jobs[j].wide == w && jobs[j].variant == v) order.push_back(j);
         int nNarrow = 0;
         while (nNarrow < gn && !jobs[order[nNarrow]].wide) nNarrow++;
         size_t off16 = 0, off32 = 0;
+        bool anyBand = false;
         for (int k = 0; k < gn; ++k) {
             PoaJob& J = jobs[order[k]];
             size_t& off = k < nNarrow ? off16 : off32;
             J.scoreOff = (long long)(off / (J.wide ? 4 : 2));
-            off += jobBytes(J);
+            off += jobBytes(J, order[k]);
+            anyBand = anyBand || J.variant == kBandVariant;
+        }
+        std::vector<int> hBandOf;   // group position -> BandJob; read by the copy until the fill's sync
+        if (anyBand) {
+            hBandOf.resize(gn);
+            for (int k = 0; k < gn; ++k) hBandOf[k] = bandOf[order[k]];
+            dBandOf_.reserve(gn, false);
+            check(hipMemcpyAsync(dBandOf_.ptr, hBandOf.data(), gn * sizeof(int), hipMemcpyHostToDevice, stream_),
+                  "upload");
         }
         dPool_.reserve((off16 + off32 + 256 + 7) / 8, false);
         // the group's jobs in launch order: [nJobs, nJobs + gn) of the pinned job array
@@ -711,6 +1383,10 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
         for (int k = 0; k < gn;) {   // one launch per (width, variant) run
             int e = k;
             while (e < gn && gj[e].wide == gj[k].wide && gj[e].variant == gj[k].variant) e++;
+            if (gj[k].variant == kBandVariant) {   // timed on its own below
+                k = e;
+                continue;
+            }
             if (gj[k].wide) {
                 launch_fill<int>(0, e - k, k, stream_, dJobs_.ptr, pools, pool32, dScore_.ptr, dExitCol_.ptr);
             } else if (gj[k].variant == 0) {
@@ -726,38 +1402,91 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
         }
         check(hipGetLastError(), "k_poa_fill launch");
         if (profiling) check(hipEventRecord(ev_[1], stream_), "event");
+        if (anyBand) {
+            if (profiling) check(hipEventRecord(bev_[0], stream_), "event");
+            for (int k = 0; k < gn;) {
+                int e = k;
+                while (e < gn && gj[e].wide == gj[k].wide && gj[e].variant == gj[k].variant) e++;
+                if (gj[k].variant == kBandVariant) {
+                    // LDS: the ring, and the launch's longest read up to kBandReadLds bytes
+                    int ldsRead = 0;
+                    for (int x = k; x < e; ++x) ldsRead = std::max(ldsRead, gj[x].I + 1);
+                    ldsRead = std::min((ldsRead + 15) / 16 * 16, kBandReadLds);
+                    const size_t ring = (size_t)kBandRing * kBandSlot;
+                    if (gj[k].wide)
+                        hipLaunchKernelGGL(k_poa_fill_band<int>, dim3(e - k), dim3(64), ring * sizeof(int) + ldsRead,
+                                           stream_, dJobs_.ptr, dBandOf_.ptr, dBand_.ptr, k, pools, dRange_.ptr,
+                                           dCellOff_.ptr, pool32, dScore_.ptr, dExitCol_.ptr, ldsRead);
+                    else
+                        hipLaunchKernelGGL(k_poa_fill_band<uint16_t>, dim3(e - k), dim3(64),
+                                           ring * sizeof(uint16_t) + ldsRead, stream_, dJobs_.ptr, dBandOf_.ptr,
+                                           dBand_.ptr, k, pools, dRange_.ptr, dCellOff_.ptr, pool16, dScore_.ptr,
+                                           dExitCol_.ptr, ldsRead);
+                    stats.launches++;
+                }
+                k = e;
+            }
+            check(hipGetLastError(), "k_poa_fill_band launch");
+            if (profiling) check(hipEventRecord(bev_[1], stream_), "event");
+        }
         check(hipMemcpyAsync(hScore_.ptr, dScore_.ptr, gn * sizeof(int), hipMemcpyDeviceToHost, stream_), "d2h");
         check(hipStreamSynchronize(stream_), "k_poa_fill");
         if (profiling) {
             float ms = 0.f;
             check(hipEventElapsedTime(&ms, ev_[0], ev_[1]), "event");
             stats.fillMs += ms;
+            if (anyBand) {
+                check(hipEventElapsedTime(&ms, bev_[0], bev_[1]), "event");
+                band.fillMs += ms;
+            }
         }
         for (int k = 0; k < gn; ++k) {
             const PoaJob& J = gj[k];
             (*out)[jobReq[order[k]]].score[jobOri[order[k]]] = (float)hScore_.ptr[k];
             stats.alignments++;
+            if (J.variant == kBandVariant) {
+                const long long c = bandCells[order[k]];
+                band.bandedAlignments++;
+                band.bandCells += c;
+                band.fullCells += (long long)J.nCols * (J.I + 1);
+                band.scoreBytes += (double)c * (J.wide ? 4 : 2);
+                stats.cells += c;
+                stats.bytes += (double)c * (J.wide ? 4 : 2);
+                continue;
+            }
             stats.cells += (long long)J.nCols * (J.I + 1);
             stats.bytes += (double)J.nCols * (J.I + 1) * (J.wide ? 4 : 2);
         }
         // SparsePoa's choice (src/SparsePoa.cpp:112-131) / AddRead's unconditional commit (PoaGraphImpl.cpp:354-369)
         for (int r = r0; r < r1; ++r) {
             AlignResult& R = (*out)[r];
-            if (!reqs[r].orient) R.chosen = 0;
+            if (reqs[r].tryOnly >= 0) R.chosen = oriOf(r, 0);
+            else if (!reqs[r].orient) R.chosen = 0;
             else if (R.score[0] >= R.score[1] && R.score[0] >= reqs[r].minScore) R.chosen = 0;
             else if (R.score[1] >= R.score[0] && R.score[1] >= reqs[r].minScore) R.chosen = 1;
         }
-        // traceback of the committed jobs (positions in the group's launch order), uint16 first
-        std::vector<int> traceNarrow, traceWide;
+        // traceback of the committed jobs (positions in the group's launch order), uint16 first, then the banded
+        // ones the same way
+        std::vector<int> traceNarrow, traceWide, traceBand[2];
         for (int k = 0; k < gn; ++k)
-            if ((*out)[jobReq[order[k]]].chosen == jobOri[order[k]]) (k < nNarrow ? traceNarrow : traceWide).push_back(k);
-        const int tn = (int)traceNarrow.size(), tw = (int)traceWide.size(), nt = tn + tw;
+            if ((*out)[jobReq[order[k]]].chosen == jobOri[order[k]]) {
+                if (gj[k].variant == kBandVariant) traceBand[gj[k].wide ? 1 : 0].push_back(k);
+                else (k < nNarrow ? traceNarrow : traceWide).push_back(k);
+            }
+        const int tn = (int)traceNarrow.size(), tw = (int)traceWide.size();
+        const int tb0 = (int)traceBand[0].size(), tb1 = (int)traceBand[1].size(), nt = tn + tw + tb0 + tb1;
+        auto traceAt = [&](int t) {
+            if (t < tn) return traceNarrow[t];
+            if (t < tn + tw) return traceWide[t - tn];
+            if (t < tn + tw + tb0) return traceBand[0][t - tn - tw];
+            return traceBand[1][t - tn - tw - tb0];
+        };
         if (nt > 0) {
             hTraceJobs_.reserve(nt);
             long long stepTotal = 0;
             std::vector<long long> stepOff(nt);
             for (int t = 0; t < nt; ++t) {
-                const int k = t < tn ? traceNarrow[t] : traceWide[t - tn];
+                const int k = traceAt(t);
                 hTraceJobs_.ptr[t] = k;
                 gj[k].stepOff = stepTotal;
                 stepOff[t] = stepTotal;
@@ -792,6 +1521,19 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
             }
             check(hipGetLastError(), "k_poa_trace launch");
             if (profiling) check(hipEventRecord(ev_[3], stream_), "event");
+            if (tb0 + tb1 > 0) {
+                if (profiling) check(hipEventRecord(bev_[2], stream_), "event");
+                if (tb0 > 0)
+                    hipLaunchKernelGGL(k_poa_trace_band<uint16_t>, dim3(tb0), dim3(64), 0, stream_, dJobs_.ptr,
+                                       dBandOf_.ptr, dBand_.ptr, dTraceJobs_.ptr, tn + tw, pools, dRange_.ptr,
+                                       dCellOff_.ptr, pool16, dExitCol_.ptr, dSteps_.ptr, dHeads_.ptr);
+                if (tb1 > 0)
+                    hipLaunchKernelGGL(k_poa_trace_band<int>, dim3(tb1), dim3(64), 0, stream_, dJobs_.ptr, dBandOf_.ptr,
+                                       dBand_.ptr, dTraceJobs_.ptr, tn + tw + tb0, pools, dRange_.ptr, dCellOff_.ptr,
+                                       pool32, dExitCol_.ptr, dSteps_.ptr, dHeads_.ptr);
+                check(hipGetLastError(), "k_poa_trace_band launch");
+                if (profiling) check(hipEventRecord(bev_[3], stream_), "event");
+            }
             hSteps_.reserve(stepTotal);
             hHeads_.reserve(nt);
             check(hipMemcpyAsync(hHeads_.ptr, dHeads_.ptr, nt * sizeof(TraceHeader), hipMemcpyDeviceToHost, stream_),
@@ -803,12 +1545,16 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
                 float ms = 0.f;
                 check(hipEventElapsedTime(&ms, ev_[2], ev_[3]), "event");
                 stats.traceMs += ms;
+                if (tb0 + tb1 > 0) {
+                    check(hipEventElapsedTime(&ms, bev_[2], bev_[3]), "event");
+                    band.traceMs += ms;
+                }
             }
             const bool last = r1 == n;
             if (!last) keepSteps.emplace_back(hSteps_.ptr, hSteps_.ptr + stepTotal);
             const uint32_t* base = last ? hSteps_.ptr : keepSteps.back().data();
             for (int t = 0; t < nt; ++t) {
-                const int k = t < tn ? traceNarrow[t] : traceWide[t - tn];
+                const int k = traceAt(t);
                 const int r = jobReq[order[k]];
                 if (hHeads_.ptr[t].nSteps < 1) throw DeviceError("POA traceback did not reach the start vertex");
                 heads[r] = hHeads_.ptr[t];
@@ -825,6 +1571,11 @@ void PoaRunner::Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>*
     ParallelFor(n, [&](int r) {
         AlignResult& R = (*out)[r];
         if (R.chosen < 0) return;
+        if (reqs[r].tryOnly >= 0) {   // TryAddRead alone: the walk goes to the caller, the graph stays
+            R.head = heads[r];
+            R.steps.assign(stepPtr[r], stepPtr[r] + heads[r].nSteps);
+            return;
+        }
         const std::string& s = R.chosen ? rcRead[r] : reqs[r].read;
         reqs[r].graph->ThreadTraceback(s, reqs[r].mode, stepPtr[r], heads[r], &R.path);
     });
@@ -864,7 +1615,7 @@ namespace {
 // One slice [z0, z1) of a PoaBatch on one runner: lock-step read rounds over the slice's ZMWs.
 void PoaSlice(PoaRunner& R, const std::vector<std::vector<const std::string*>>& reads, int z0, int z1, long long maxCov,
               int minCov, std::vector<std::string>* consensus, std::vector<std::vector<int>>* keys,
-              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents)
+              std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents, bool banded)
 {
     const auto tStart = std::chrono::steady_clock::now();
     const int nz = z1 - z0;
@@ -896,7 +1647,7 @@ void PoaSlice(PoaRunner& R, const std::vector<std::vector<const std::string*>>& 
                     Z[z]->rc.push_back(0);
                     record(z, 0);
                 } else {
-                    reqs.push_back(AlignRequest{&Z[z]->graph, *s, kLocal, true, 0.0f});
+                    reqs.push_back(AlignRequest{&Z[z]->graph, *s, kLocal, true, 0.0f, banded});
                     reqZ.push_back(z);
                     break;
                 }
@@ -932,7 +1683,7 @@ void PoaSlice(PoaRunner& R, const std::vector<std::vector<const std::string*>>& 
 void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vector<const std::string*>>& reads,
               long long maxCov, int minCov, std::vector<std::string>* consensus, std::vector<std::vector<int>>* keys,
               std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents,
-              const std::function<void(int, int)>* afterSlice)
+              const std::function<void(int, int)>* afterSlice, bool banded)
 {
     const int nz = (int)reads.size();
     consensus->assign(nz, std::string());
@@ -957,7 +1708,7 @@ void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vec
         th.emplace_back([&, k] {
             try {
                 PoaSlice(*runners[k], reads, cut[k], std::max(cut[k], cut[k + 1]), maxCov, minCov, consensus, keys, rc,
-                         extents);
+                         extents, banded);
                 if (afterSlice) (*afterSlice)(cut[k], std::max(cut[k], cut[k + 1]));
             } catch (...) {
                 err[k] = std::current_exception();

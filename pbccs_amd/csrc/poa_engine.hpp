@@ -5,6 +5,9 @@
 // orientation) pair at once -- one wavefront per pair -- and k_poa_trace walks the chosen orientation's
 // traceback, which the host then threads into the graph.  ZmwPoa drives SparsePoa's OrientAndAddRead /
 // FindConsensus (src/SparsePoa.cpp:95-201) for a whole batch of ZMWs in lock-step read rounds.
+// Opt-in (AlignRequest::banded): a LOCAL alignment is seeded against the graph's consensus path
+// (sparse_kernels.hpp, on this runner's stream), k_poa_ranges gives every column its alignable rows, and
+// k_poa_fill_band / k_poa_trace_band store and read each column's band only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +25,7 @@
 
 #include "engine.hpp"
 #include "poa_graph.hpp"
+#include "sparse_kernels.hpp"
 
 namespace pbccs {
 namespace poa {
@@ -42,6 +46,19 @@ struct PoaJob {
     int variant;          // k_poa_fill variant (see fill_variant)
     int rowsPerLane;      // ring variants: rows per lane R; cell (column c, row i) at c * colStride + (i % R) * 64 + i / R
 };
+
+// The banded fill's view of one alignment: where its anchors, its consensus path and its
+// per-column ranges sit.  k_poa_ranges reads all of it; the banded fill and traceback read colOff only.
+struct BandJob {
+    long long anchorOff;   // the chain's first (h, v) pair in the seeding's anchor pool, in pairs
+    long long cssOff;      // into cssCol[]: the column of every consensus-path position
+    long long colOff;      // this alignment's columns in range[] (x 2), the sweeps' scratch (x 2) and cellOff[]
+    int nAnchors, cssLen;
+    int nCols, I, progOff, predStartOff, exitOff, nExit;   // as the alignment's PoaJob
+};
+
+// SdpRangeFinder's constants as ccs uses them
+constexpr int kBandK = 6;
 
 // Page-locked host staging (hipHostMalloc): the per-round program uploads and traceback downloads run at
 // DMA speed, and the buffers persist across rounds.
@@ -170,12 +187,32 @@ struct AlignRequest {
     AlignMode mode;
     bool orient;        // SparsePoa::OrientAndAddRead (also try the reverse complement)
     float minScore;     // minScoreToAdd
+    bool banded = false;   // LOCAL only: fill inside SdpRangeFinder's ranges
+    int tryOnly = -1;      // 0 / 1: TryAddRead of that orientation alone -- score and steps, nothing committed
 };
 
 struct AlignResult {
     int chosen = -1;    // 0 forward, 1 reverse complement, -1 not added
     float score[2] = {0.f, 0.f};
     std::vector<int> path;   // per read position, the vertex it was threaded through
+    bool fellBack[2] = {false, false};   // banded asked for, full fill taken (per orientation)
+    // tryOnly: the walk of that orientation as k_poa_trace reports it
+    std::vector<uint32_t> steps;
+    TraceHeader head{0, 0, 0, 0};
+};
+
+// What pbccs_sparse_poa_alignable_ranges reports for one (graph, read, orientation).
+struct RangeReport {
+    int status = 0;              // the seeding's status for the pair (PBCCS_OK, _EINVAL, _EOOM)
+    std::vector<int> cssPath;    // vertex ids
+    std::vector<int> anchors;    // (css position, read position) pairs
+    std::vector<int> ranges;     // [B, E) per vertex id; $ has none and reads (0, 0)
+};
+
+struct BandStats {
+    long long bandedAlignments = 0, fallbacks = 0, bandCells = 0, fullCells = 0, seeds = 0, anchors = 0;
+    double seedMs = 0.0, rangesMs = 0.0, fillMs = 0.0, traceMs = 0.0;   // device ms, profiling on
+    double scoreBytes = 0.0;   // score bytes the banded fills wrote
 };
 
 struct PoaStats {
@@ -198,6 +235,9 @@ public:
     // the chosen orientation.  Graphs of different requests must be distinct.
     void Align(std::vector<AlignRequest>& reqs, std::vector<AlignResult>* out);
 
+    // InitRangeFinder for one read against a graph that holds a read: consensus path, anchors, ranges.
+    void Ranges(PoaGraph* graph, const std::string& read, bool rc, RangeReport* out);
+
     void SetPoolBudget(size_t bytes) { budget_ = bytes; }
     // Unmap the score-matrix pool (the address reservation stays): the polish that follows the POA in a
     // ccs run then has the device memory to itself.
@@ -206,9 +246,16 @@ public:
     int HostThreads() const { return threads_; }
     void ParallelFor(int n, const std::function<void(int)>& f) { workers_->Run(n, f); }
     PoaStats stats;
+    BandStats band;
     bool profiling = false;
 
 private:
+    // Seeds, chains and ranges of the given alignments on the device; per alignment its band cells, or -1 when
+    // rule 5 sends it to the full fill.  cssCol: the consensus path of each alignment's request as columns.
+    void SeedAndRange(const std::vector<BandJob>& geom, const std::vector<const std::string*>& css,
+                      const std::vector<const std::string*>& read, const std::vector<int>& rc,
+                      const std::vector<const std::vector<int>*>& cssCol, const PoaPools& pools,
+                      std::vector<long long>* cells, std::vector<sparse::KeptChain>* chains);
     int device_;
     int threads_;
     std::unique_ptr<WorkerPool> workers_;
@@ -216,6 +263,11 @@ private:
     size_t budget_ = 0;   // cap on the score-matrix bytes per launch group (0 = 64 GB); also <= 0.6 x free HBM
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t bev_[4] = {nullptr, nullptr, nullptr, nullptr};   // the banded kernels' phases
+    std::unique_ptr<sparse::SparseRunner> seeder_;   // on stream_
+    DevVec<BandJob> dBand_;
+    DevVec<int> dCssCol_, dRange_, dFwd_, dAcc_, dBandOf_;
+    DevVec<long long> dCellOff_, dCells_;
     DevVec<uint8_t> dBase_, dRowBase_;
     VmPool dPool_;   // score matrices: 1 GB granules mapped as rounds grow, never copied or freed between rounds
     DevVec<int> dVertexOfCol_, dPredStart_, dPredCol_, dExitPred_, dScore_, dExitCol_, dTraceJobs_;
@@ -244,12 +296,13 @@ struct ZmwPoa {
 // taken; keys[z][r] = key, -2 past the coverage stop.  minCov < 0: (cov < 5) ? 1 : (cov + 1) / 2 - 1.
 // The ZMWs are split into one slice per runner (about equal read bases each); the slices run concurrently,
 // so one slice's host work (column programs, threading) overlaps the other's kernels.
+// banded: every alignment is filled inside SdpRangeFinder's ranges unless rule 5 sends it back.
 // afterSlice (optional) is called on a slice's thread with its ZMW range [z0, z1) once that slice's outputs are
 // final, while the other slices may still be running.
 void PoaBatch(const std::vector<PoaRunner*>& runners, const std::vector<std::vector<const std::string*>>& reads,
               long long maxCov, int minCov, std::vector<std::string>* consensus, std::vector<std::vector<int>>* keys,
               std::vector<std::vector<char>>* rc, std::vector<std::vector<int>>* extents,
-              const std::function<void(int, int)>* afterSlice = nullptr);
+              const std::function<void(int, int)>* afterSlice = nullptr, bool banded = false);
 
 }  // namespace poa
 }  // namespace pbccs

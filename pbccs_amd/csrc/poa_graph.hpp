@@ -209,6 +209,12 @@ public:
     {
         ColumnProgram P;
         Program(&P);
+        return ConsensusPath(mode, minCoverage, P);
+    }
+
+    // the same over a column program of this graph the caller already holds
+    std::vector<int> ConsensusPath(AlignMode mode, int minCoverage, const ColumnProgram& P)
+    {
         const int total = (int)numReads_;
         std::vector<int> bestPrev(v_.size(), -1);
         v_[kEnter].reaching = 0;

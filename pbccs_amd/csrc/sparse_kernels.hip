@@ -505,10 +505,10 @@ long long env_ll(const char* name, long long dflt)
 
 }  // namespace
 
-SparseRunner::SparseRunner(int device) : device_(device)
+SparseRunner::SparseRunner(int device, hipStream_t stream) : device_(device), stream_(stream), ownStream_(!stream)
 {
     check(hipSetDevice(device_), "hipSetDevice");
-    check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
+    if (ownStream_) check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
     for (auto& e : ev_) check(hipEventCreate(&e), "hipEventCreate");
 }
 
@@ -516,13 +516,33 @@ SparseRunner::~SparseRunner()
 {
     if (stream_) {
         (void)hipStreamSynchronize(stream_);
-        (void)hipStreamDestroy(stream_);
+        if (ownStream_) (void)hipStreamDestroy(stream_);
     }
     for (auto& e : ev_)
         if (e) (void)hipEventDestroy(e);
 }
 
 void SparseRunner::Run(int k, const SparseInput* in, int n, std::vector<SparseResult>* out)
+{
+    RunImpl(k, in, n, out, nullptr);
+}
+
+void SparseRunner::RunKeep(int k, const SparseInput* in, int n, std::vector<KeptChain>* out)
+{
+    std::vector<SparseResult> res;
+    out->assign((size_t)std::max(0, n), KeptChain());
+    RunImpl(k, in, n, &res, out);
+    for (int g = 0; g < n; ++g) {
+        (*out)[g].status = res[g].status;
+        (*out)[g].nSeeds = res[g].nSeeds;
+        (*out)[g].nAnchors = res[g].status == PBCCS_OK ? res[g].nAnchors : 0;
+    }
+}
+
+// keep: the chains stay on the device; each chunk's anchor room then follows the previous chunk's in dAnchors_,
+// which is sized for the whole call up front
+void SparseRunner::RunImpl(int k, const SparseInput* in, int n, std::vector<SparseResult>* out,
+                           std::vector<KeptChain>* keep)
 {
     out->assign((size_t)std::max(0, n), SparseResult());
     if (n <= 0) return;
@@ -564,14 +584,21 @@ void SparseRunner::Run(int k, const SparseInput* in, int n, std::vector<SparseRe
         ~StreamIdle() { (void)hipStreamSynchronize(s); }
     } idle{stream_};
 
+    long long keptPairs = 0;   // keep: the anchor room of the chunks before this one
+    if (keep) {
+        long long all = 0;
+        for (int g : live) all += std::max(0, std::min(in[g].len1, in[g].len2) - k + 1);
+        dAnchors_.reserve((size_t)std::max(1LL, 2 * all), false);
+    }
     size_t at = 0;
     while (at < live.size()) {
         // one chunk: as many jobs as keep the position arrays within half the budget
         std::vector<SparseJob> jobs;
         std::vector<int> owner;
-        long long posInts = 0, seqBytes = 0, anchorPairs = 0, rangeInts = 0;
+        long long posInts = 0, seqBytes = 0, anchorPairs = keptPairs, rangeInts = 0;
         while (at < live.size()) {
-            const SparseInput& s = in[live[at]];
+            SparseInput s = in[live[at]];
+            if (keep) s.ranges = nullptr;
             const long long need = Layout(s.len1, s.len2, k).total + (s.ranges ? 2LL * s.len1 : 0);
             if (!jobs.empty() && posInts + rangeInts + need > halfInts) break;
             SparseJob jb;
@@ -690,9 +717,10 @@ void SparseRunner::Run(int k, const SparseInput* in, int n, std::vector<SparseRe
         }
         if (profiling) check(hipEventRecord(ev_[3], stream_), "event");
         std::vector<SparseOut> hOut((size_t)na);
-        std::vector<int> hAnchors((size_t)std::max(1LL, 2 * anchorPairs)), hRanges((size_t)std::max(1LL, rangeInts));
+        std::vector<int> hAnchors((size_t)std::max(1LL, keep ? 1 : 2 * anchorPairs)),
+            hRanges((size_t)std::max(1LL, rangeInts));
         check(hipMemcpyAsync(hOut.data(), dOut_.ptr, sizeof(SparseOut) * na, hipMemcpyDeviceToHost, stream_), "download");
-        if (anchorPairs)
+        if (anchorPairs && !keep)
             check(hipMemcpyAsync(hAnchors.data(), dAnchors_.ptr, sizeof(int) * 2 * anchorPairs, hipMemcpyDeviceToHost,
                                  stream_),
                   "download");
@@ -705,6 +733,7 @@ void SparseRunner::Run(int k, const SparseInput* in, int n, std::vector<SparseRe
             check(hipEventElapsedTime(&ms, ev_[2], ev_[3]), "event");
             stats.deviceMs += ms;
         }
+        if (keep) keptPairs = anchorPairs;
         for (int j = 0; j < na; ++j) {
             const SparseInput& s = in[activeOwner[j]];
             SparseResult& r = (*out)[activeOwner[j]];
@@ -713,6 +742,10 @@ void SparseRunner::Run(int k, const SparseInput* in, int n, std::vector<SparseRe
             r.nAnchors = o.nAnchors;
             r.score = o.score;
             stats.anchors += o.nAnchors;
+            if (keep) {
+                (*keep)[activeOwner[j]].anchorOff = jb.anchorOff + o.anchorStart;
+                continue;
+            }
             if (o.nAnchors > s.anchorCap || (o.nAnchors > 0 && !s.anchors)) r.status = PBCCS_ERANGE;
             else if (o.nAnchors > 0)
                 std::memcpy(s.anchors, hAnchors.data() + 2 * (jb.anchorOff + o.anchorStart), sizeof(int) * 2 * o.nAnchors);

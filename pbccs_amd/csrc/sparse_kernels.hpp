@@ -101,9 +101,18 @@ struct SparseStats {
     double deviceMs = 0.0;                      // all five kernels, profiling on
 };
 
+// One pair whose chain stays on the device (RunKeep): what the host may know of it.
+struct KeptChain {
+    int status = 0;
+    int nAnchors = 0;
+    long long nSeeds = 0;
+    long long anchorOff = 0;   // the chain's first (h, v) pair in AnchorsDevice(), in pairs
+};
+
 class SparseRunner {
 public:
-    explicit SparseRunner(int device);
+    // stream: the caller's stream to run on (the POA runner's); nullptr creates one
+    explicit SparseRunner(int device, hipStream_t stream = nullptr);
     ~SparseRunner();
     SparseRunner(const SparseRunner&) = delete;
     SparseRunner& operator=(const SparseRunner&) = delete;
@@ -115,12 +124,20 @@ public:
     // launch groups whose arrays fit the budget.
     void Run(int k, const SparseInput* in, int n, std::vector<SparseResult>* out);
 
+    // The same for a consumer on the device: no anchor or range leaves it (the inputs' anchors / ranges are not
+    // read), every chain of the call stays in AnchorsDevice() until the next call, and the host learns each
+    // pair's status, seed count, chain length and the chain's place.
+    void RunKeep(int k, const SparseInput* in, int n, std::vector<KeptChain>* out);
+    const int* AnchorsDevice() const { return dAnchors_.ptr; }
+
     SparseStats stats;
     bool profiling = false;
 
 private:
+    void RunImpl(int k, const SparseInput* in, int n, std::vector<SparseResult>* out, std::vector<KeptChain>* keep);
     int device_;
     hipStream_t stream_ = nullptr;
+    bool ownStream_ = true;
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
     DevVec<uint8_t> dSeq_;
     DevVec<SparseJob> dJobs_, dActive_;

@@ -146,16 +146,18 @@ def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None):
     return None, {"draft": draft, "snr": list(chunk["snr"]), "reads": out}
 
 
-def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, map_past_cap=False):
+def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, map_past_cap=False,
+                     banded_poa=False):
     """zmw_input for many ZMWs at once, with the POA of all of them on the GPU in one pbccs_poa_batch
     (every ZMW adds its next subread in the same device round).  Returns [(status, zmw)] as zmw_input.
-    map_past_cap: the reads past max_poa_coverage of all ZMWs are placed on their drafts in one pbccs_map_batch."""
+    map_past_cap: the reads past max_poa_coverage of all ZMWs are placed on their drafts in one pbccs_map_batch.
+    banded_poa: the POA fills inside SdpRangeFinder's ranges (poa.poa_batch(banded=True))."""
     from . import poa as _poa
     filtered = [filter_reads(c["reads"], min_length) for c in chunks]
     idx = [z for z, rs in enumerate(filtered) if rs and not all(r is None for r in rs)]
     out = [("NoSubreads", None)] * len(chunks)
     res = _poa.poa_batch([[None if r is None else r["seq"] for r in filtered[z]] for z in idx],
-                         max_coverage=max_poa_coverage, engine=engine)
+                         max_coverage=max_poa_coverage, engine=engine, banded=banded_poa)
     past = {}
     if map_past_cap:
         from . import mapping as _mapping
@@ -182,7 +184,7 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
     return out
 
 
-def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False):
+def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -193,6 +195,8 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     the order of ZScores() and of the ccs.bam zs tag.
     map_past_cap (pbccs_ccs_batch_ex): the reads past the maxPoaCov stop are placed on the draft on the GPU
     (mapping.map_to_draft's aligner) and reach AddRead like the POA's reads, in FilterReads' order.
+    banded_poa (pbccs_ccs_batch_ex2): the draft's alignments are filled inside SdpRangeFinder's ranges
+    (poa.poa_batch(banded=True)); everything after the draft is unchanged.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -253,7 +257,13 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         outs["add_order"][:n] = order.ctypes.data + 4 * f0
     opts = settings._c()
     mc = 2**62 if max_poa_coverage is None else int(max_poa_coverage)
-    if map_past_cap:
+    if banded_poa:
+        co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
+        po = L.CPoaOptions(mc, -1, 1)
+        L.check(L.load().pbccs_ccs_batch_ex2(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                             ctypes.byref(co), ctypes.byref(po), ctypes.byref(opts),
+                                             ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    elif map_past_cap:
         co = L.CCcsOptions(mc, 1)
         L.check(L.load().pbccs_ccs_batch_ex(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
                                             ctypes.byref(co), ctypes.byref(opts),

@@ -202,6 +202,17 @@ class CCcsOptions(ctypes.Structure):
     _fields_ = [("max_poa_coverage", ctypes.c_longlong), ("map_past_cap", ctypes.c_int)]
 
 
+class CPoaOptions(ctypes.Structure):
+    _fields_ = [("max_coverage", ctypes.c_longlong), ("min_coverage", ctypes.c_int), ("banded", ctypes.c_int)]
+
+
+class CPoaBandStats(ctypes.Structure):
+    _fields_ = [("banded_alignments", ctypes.c_longlong), ("fallbacks", ctypes.c_longlong),
+                ("band_cells", ctypes.c_longlong), ("full_cells", ctypes.c_longlong), ("seeds", ctypes.c_longlong),
+                ("anchors", ctypes.c_longlong), ("seed_ms", ctypes.c_double), ("ranges_ms", ctypes.c_double),
+                ("fill_ms", ctypes.c_double), ("trace_ms", ctypes.c_double), ("score_bytes", ctypes.c_double)]
+
+
 class CSparseAlignInput(ctypes.Structure):
     _fields_ = [("target", ctypes.c_char_p), ("target_len", ctypes.c_int), ("query", ctypes.c_char_p),
                 ("query_len", ctypes.c_int), ("reverse_complement", ctypes.c_int),
@@ -337,6 +348,20 @@ SIGNATURES = {
     "pbccs_sparse_align_batch": (I, [P, I, ctypes.POINTER(CSparseAlignInput), I,
                                      ctypes.POINTER(CSparseAlignOutput)]),
     "pbccs_sparse_align_stats_get": (I, [P, ctypes.POINTER(CSparseAlignStats), I]),
+    # banded POA fill
+    "pbccs_poa_options_default": (None, [ctypes.POINTER(CPoaOptions)]),
+    "pbccs_poa_batch_ex": (I, [P, ctypes.POINTER(CPoaInput), I, ctypes.POINTER(CPoaOptions),
+                               ctypes.POINTER(CPoaOutput)]),
+    "pbccs_sparse_poa_set_banded": (I, [P, I]),
+    "pbccs_sparse_poa_alignable_ranges": (I, [P, ctypes.c_char_p, I, I, PI, I, PI, PI, I, PI, PI, I, PI, PI]),
+    "pbccs_sparse_poa_try_add_read": (I, [P, ctypes.c_char_p, I, I, I, PF, PI, I, PI]),
+    "pbccs_poa_band_stats_get": (I, [P, ctypes.POINTER(CPoaBandStats), I]),
+}
+# bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
+DIGIT_SIGNATURES = {
+    "pbccs_ccs_batch_ex2": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                                ctypes.POINTER(CPoaOptions), ctypes.POINTER(CPolishOptions),
+                                ctypes.POINTER(CCcsOutput)]),
 }
 
 
@@ -347,7 +372,7 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise PbccsError(-3, f"{LIB_PATH} is missing: run __graft_entry__.build() (no CPU fallback exists)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(DIGIT_SIGNATURES.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args

@@ -12,6 +12,8 @@ from .lib import load
 
 GLOBAL, SEMIGLOBAL, LOCAL = 0, 1, 2
 COLOR_NODES, VERBOSE_NODES = 1, 2
+# moves of a traceback step (PoaGraphImpl.hpp:45-55), as SparsePoa.TryAddRead reports them
+START_MOVE, END_MOVE, MATCH_MOVE, MISMATCH_MOVE, DELETE_MOVE, EXTRA_MOVE = 1, 2, 3, 4, 5, 6
 INT_MAX = 2**31 - 1
 
 
@@ -38,15 +40,20 @@ def _text(fn, first=1 << 16):
 
 
 class SparsePoa:
-    """PacBio::CCS::SparsePoa: OrientAndAddRead and FindConsensus with PoaAlignmentSummary extents."""
+    """PacBio::CCS::SparsePoa: OrientAndAddRead and FindConsensus with PoaAlignmentSummary extents.
+    banded=True: every alignment is filled inside SdpRangeFinder's ranges."""
 
-    def __init__(self, engine=None):
+    def __init__(self, engine=None, banded=False):
         self._eng = _engine(engine)
         h = ctypes.c_void_p()
         _L.check(load().pbccs_sparse_poa_create(self._eng._h, ctypes.byref(h)))
         self._h = h
         self._lib = load()
         self._n = 0
+        self._bases = 0
+        self.banded = bool(banded)
+        if banded:
+            _L.check(load().pbccs_sparse_poa_set_banded(self._h, 1))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -59,7 +66,40 @@ class SparsePoa:
         _L.check(load().pbccs_sparse_poa_orient_and_add_read(self._h, b, len(b), min_score_to_add, ctypes.byref(key)))
         if key.value >= 0:
             self._n += 1
+            self._bases += len(b)
         return key.value
+
+    def AlignableRanges(self, seq, rc=False):
+        """What the range finder sees for this read against the current graph: {"css_path": vertex ids,
+        "anchors": [(css position, read position)], "ranges": {vertex id: (B, E)}, "fallback": bool}.  With
+        fallback (no anchors, a foreign letter, seeding out of memory) anchors and ranges are empty."""
+        b = seq.encode()
+        nv = self._bases + 2   # a graph never has more vertices than the bases added, ^ and $
+        css = (ctypes.c_int * nv)()
+        anchors = (ctypes.c_int * (2 * max(1, len(b))))()
+        ranges = (ctypes.c_int * (2 * nv))()
+        nc, na, nr, fb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _L.check(load().pbccs_sparse_poa_alignable_ranges(
+            self._h, b, len(b), 1 if rc else 0, css, nv, ctypes.byref(nc), anchors, max(1, len(b)), ctypes.byref(na),
+            ranges, nv, ctypes.byref(nr), ctypes.byref(fb)))
+        rg = {v: (ranges[2 * v], ranges[2 * v + 1]) for v in range(nr.value) if v != 1}
+        return {"css_path": list(css[:nc.value]),
+                "anchors": [(anchors[2 * k], anchors[2 * k + 1]) for k in range(na.value)],
+                "ranges": rg, "fallback": bool(fb.value)}
+
+    def TryAddRead(self, seq, rc=False, banded=None, rows=False):
+        """TryAddRead without the commit: (exit score, [(vertex, move)]) in k_poa_trace's order -- the End move
+        into $ first, the Start move last.  banded=None takes the handle's switch; rows=True gives
+        (vertex, move, row of the visited cell) per step."""
+        b = seq.encode()
+        cap = len(b) + self._bases + 4
+        steps = (ctypes.c_int * (3 * cap))()
+        score, n = ctypes.c_float(), ctypes.c_int()
+        use = self.banded if banded is None else bool(banded)
+        _L.check(load().pbccs_sparse_poa_try_add_read(self._h, b, len(b), 1 if rc else 0, 1 if use else 0,
+                                                      ctypes.byref(score), steps, cap, ctypes.byref(n)))
+        w = 3 if rows else 2
+        return score.value, [tuple(steps[3 * k:3 * k + w]) for k in range(n.value)]
 
     # the Consensus.h / driver.py surface
     orient_and_add_read = OrientAndAddRead
@@ -101,10 +141,11 @@ def poa_consensus(reads, mode=GLOBAL, min_coverage=-INT_MAX, graphviz_flags=None
     return (seq, dot.raw[:dn.value].decode()) if dot is not None else seq
 
 
-def poa_batch(zmw_reads, max_coverage=None, min_coverage=-1, engine=None):
+def poa_batch(zmw_reads, max_coverage=None, min_coverage=-1, engine=None, banded=False):
     """Consensus.h's PoaConsensus for many ZMWs at once.  zmw_reads: per ZMW, the subreads in FilterReads
     order (None = dropped).  Returns per ZMW {"consensus", "keys" (per read: key, -1, or -2 past
-    maxPoaCov), "summaries" (per key: rc, read, tpl extents)}.
+    maxPoaCov), "summaries" (per key: rc, read, tpl extents)}.  banded=True (pbccs_poa_batch_ex) fills every
+    alignment inside SdpRangeFinder's ranges.
 
     Marshalling is flat: all reads in one buffer with a pointer table, all outputs in shared arrays, so
     the per-ZMW Python work is a few struct-field stores."""
@@ -146,8 +187,13 @@ def poa_batch(zmw_reads, max_coverage=None, min_coverage=-1, engine=None):
         outs["rc"][:n] = rc.ctypes.data + 4 * f0
         outs["extents"][:n] = ext.ctypes.data + 16 * f0
     mc = 2**62 if max_coverage is None else int(max_coverage)
-    _L.check(load().pbccs_poa_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CPoaInput)), n, mc,
-                                    int(min_coverage), ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CPoaOutput))))
+    if banded:
+        po = _L.CPoaOptions(mc, int(min_coverage), 1)
+        _L.check(load().pbccs_poa_batch_ex(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CPoaInput)), n,
+                                           ctypes.byref(po), ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CPoaOutput))))
+    else:
+        _L.check(load().pbccs_poa_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CPoaInput)), n, mc,
+                                        int(min_coverage), ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CPoaOutput))))
     raw = cbuf.raw
     firsts, cnts, nks = first.tolist(), counts.tolist(), outs["n_keys"][:n].tolist()
     cs, lns = cstart.tolist(), outs["len"][:n].tolist()
@@ -168,3 +214,11 @@ def poa_stats(engine=None, reset=False):
     s = _L.CPoaStats()
     _L.check(load().pbccs_poa_stats_get(eng._h, ctypes.byref(s), 1 if reset else 0))
     return {k: getattr(s, k) for k, _ in _L.CPoaStats._fields_}
+
+
+def poa_band_stats(engine=None, reset=False):
+    """Banded-fill work since the last reset (pbccs_poa_band_stats)."""
+    eng = _engine(engine)
+    s = _L.CPoaBandStats()
+    _L.check(load().pbccs_poa_band_stats_get(eng._h, ctypes.byref(s), 1 if reset else 0))
+    return {k: getattr(s, k) for k, _ in _L.CPoaBandStats._fields_}
