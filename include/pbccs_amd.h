@@ -835,6 +835,99 @@ typedef struct {
 } pbccs_poa_band_stats;
 int pbccs_poa_band_stats_get(pbccs_engine* eng, pbccs_poa_band_stats* out, int reset);
 
+/* ---- Windowed polish: a long draft polished as overlapping windows and stitched ------------------------
+ * An opt-in with no counterpart in the reference (DESIGN.md §3.18 states the rules).  A draft longer than
+ * window + overlap is cut into n = ceil((L - overlap) / window) windows of step S = ceil((L - overlap) / n),
+ * window i = [i S, min(L, i S + S + overlap)).  Every read is cut at the window boundaries through its
+ * SparseAlign<k> chain against the draft (on the device; only the cuts come back), each window is polished as an
+ * ordinary ZMW by pbccs_polish_batch with the caller's settings, and neighbouring windows are joined at a draft
+ * position of their overlap around which both windows' Align transcripts (window draft -> window consensus,
+ * GLOBAL, 0 -1 -1 -1) hold 2 guard neighbouring M.  A ZMW with a window that is not PBCCS_ZMW_SUCCESS, without a
+ * join, or whose stitched predicted accuracy misses min_predicted_accuracy is polished whole instead, and its
+ * record is the whole-template route's. */
+typedef struct {
+    int window;    /* W (2000) */
+    int overlap;   /* V (200) */
+    int guard;     /* g (8) */
+    int k;         /* the seeds' K (6) */
+} pbccs_window_options;
+void pbccs_window_options_default(pbccs_window_options* o);
+/* valid: window > overlap, overlap >= 2 guard, guard >= 1, 4 <= k <= 8; anything else is PBCCS_EINVAL before any
+ * device work in every call below */
+
+#define PBCCS_WINDOW_FALLBACK_NONE 0
+#define PBCCS_WINDOW_FALLBACK_WINDOW 1     /* a window's status was not PBCCS_ZMW_SUCCESS */
+#define PBCCS_WINDOW_FALLBACK_NO_JOIN 2    /* two neighbouring windows have no join, or the joins cross */
+#define PBCCS_WINDOW_FALLBACK_ACCURACY 3   /* the stitched predicted accuracy is below min_predicted_accuracy */
+
+/* Host only.  bounds receives 2 * *n_windows ints (begin, end); PBCCS_ERANGE when cap (in windows) is too small,
+ * *n_windows set (bounds may be NULL with cap 0 to size the call). */
+int pbccs_window_plan(int draft_len, const pbccs_window_options* w, int* bounds, int cap, int* n_windows);
+
+/* Host only: the join rule on two transcripts (M R I D; target = the window's draft, query = its consensus) of
+ * the windows [begin_a, end_a) and [begin_b, end_b), begin_a < begin_b.  Candidates p in [begin_b + guard,
+ * end_a - guard] in the order mid, mid + 1, mid - 1, ... with mid = (begin_b + end_a) / 2; the first p whose draft
+ * columns p - guard .. p + guard - 1 are taken by 2 guard neighbouring M of both transcripts is the join:
+ * *found = 1, *p, and *cut_a / *cut_b = TargetToQueryPositions(transcript)[p - begin].  PBCCS_EINVAL for a
+ * transcript that does not span its window or holds another character. */
+int pbccs_window_join(const char* transcript_a, int len_a, int begin_a, int end_a, const char* transcript_b,
+                      int len_b, int begin_b, int end_b, int guard, int* found, int* p, int* cut_a, int* cut_b);
+
+/* The reads' slices per window.  n_windows[z] windows per ZMW; slices holds, ZMW after ZMW, n_windows[z] *
+ * n_reads ints[4] in (window, read) order: the slice [begin, end) in the read's forward text (its sequence for
+ * strand 0, the reverse complement for strand 1) and the read's mapped extent [ts', te') in window coordinates,
+ * or -1 -1 -1 -1 where the read is a placeholder in that window (no sequence, an empty chain, a slice or extent
+ * shorter than min_length).  A ZMW with one window reports its reads as they are.  unanchored[z] (may be NULL):
+ * reads with a sequence and no chain.  *n_ints = the ints needed; PBCCS_ERANGE when cap is smaller (slices may be
+ * NULL with cap 0 to size the call; nothing runs on the device then). */
+int pbccs_window_slices(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_window_options* w,
+                        int min_length, int* n_windows, int* slices, long long cap, long long* n_ints,
+                        int* unanchored);
+
+typedef struct {
+    int begin, end;          /* draft bounds */
+    int join;                /* the draft position of the join with the next window; -1: none (the last window) */
+    int cut_begin, cut_end;  /* the piece [cut_begin, cut_end) of the window's consensus in the stitched one */
+    int status;              /* PBCCS_ZMW_* of the window */
+    long long n_tested, n_applied;
+} pbccs_window_record;
+
+typedef struct {
+    int n_windows;
+    int fallback;            /* PBCCS_WINDOW_FALLBACK_* */
+    int unanchored_reads;
+    pbccs_window_record* windows;   /* caller buffer of windows_cap records (may be NULL); the first
+                                       min(n_windows, windows_cap) are written */
+    int windows_cap;
+} pbccs_window_info;
+
+/* pbccs_polish_batch with windows.  A ZMW with one window goes through the first pbccs_polish_batch call beside
+ * the windows and its record is pbccs_polish_batch's; all fallbacks of the call share a second one.  The stitched
+ * record: consensus and qvs are the pieces; predicted_accuracy as Consensus.h:508-512 over the stitched QVs;
+ * n_tested / n_applied the sums over the windows (mutations of an overlap count in both windows);
+ * add_read_results[r] the first code other than SUCCESS among the windows the read takes part in, in window
+ * order, else SUCCESS (-1 when it takes part in none); zscores[r] the minimum over its windows (NaN in none); za
+ * the mean of the SUCCESS reads' zscores; zg the minimum of the windows' zg; n_passes and status_counts from the
+ * per-read codes.  info (may be NULL): n entries. */
+int pbccs_polish_windowed(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                          const pbccs_window_options* w, pbccs_zmw_output* out, pbccs_window_info* info);
+
+/* pbccs_ccs_batch_ex2 whose polish is pbccs_polish_windowed: win NULL is pbccs_ccs_batch_ex2.  With windows every
+ * chunk is drafted first and the chunks are then polished one after another.  info (may be NULL): n entries,
+ * written for the ZMWs that reach the polish (n_windows 0 otherwise). */
+int pbccs_ccs_batch_ex3(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_window_options* win,
+                        const pbccs_polish_options* opts, pbccs_ccs_output* out, pbccs_window_info* info);
+
+/* Windowed-polish work since the last reset: multi-window ZMWs, their windows, fallbacks by reason, reads without
+ * a chain, kernel launches, and host wall time by phase (seeds and cuts, the windows' polish, align and join, the
+ * fallbacks' polish). */
+typedef struct {
+    long long zmws, windows, fallbacks[4], unanchored_reads, cut_tasks, joints, launches;
+    double slices_ms, polish_ms, join_ms, fallback_ms;
+} pbccs_window_stats;
+int pbccs_window_stats_get(pbccs_engine* eng, pbccs_window_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -300,7 +300,7 @@ def QVsToASCII(qvs):
 
 
 from .polish import (ConsensusSettings, PreparedBatch, plan_batches, polish_many, polish_stream,  # noqa: E402
-                     polish_zmws)  # batched ccs driver
+                     polish_windowed, polish_zmws)  # batched ccs driver
 from . import quiver as _quiver  # noqa: E402
 from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E402,F401
                      QuiverMultiReadMutationScorer, QvEvaluator, QvSequenceFeatures, ALL_MOVES, BASIC_MOVES,
@@ -315,6 +315,6 @@ from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa:
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",
-    "PbccsError", "QVsToASCII", "RefineConsensus", "polish_many", "polish_zmws", "polish_stream", "plan_batches", "INSERTION", "DELETION", "SUBSTITUTION",
+    "PbccsError", "QVsToASCII", "RefineConsensus", "polish_many", "polish_zmws", "polish_stream", "polish_windowed", "plan_batches", "INSERTION", "DELETION", "SUBSTITUTION",
     "FORWARD_STRAND", "REVERSE_STRAND",
 ]

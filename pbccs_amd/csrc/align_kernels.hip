@@ -421,6 +421,21 @@ AlignRunner::~AlignRunner()
 
 void AlignRunner::Run(const AlignScoring& p, const PairView* pairs, int n, PairResult* out)
 {
+    RunImpl(p, pairs, n, out, nullptr);
+}
+
+void AlignRunner::RunKeep(const AlignScoring& p, const PairView* pairs, int n, std::vector<KeptTranscript>* out)
+{
+    std::vector<PairResult> res((size_t)std::max(0, n));
+    out->assign((size_t)std::max(0, n), KeptTranscript());
+    RunImpl(p, pairs, n, res.data(), out);
+    for (int k = 0; k < n; ++k) (*out)[k].status = res[k].status;
+}
+
+// keep: the reversed transcripts stay in dOut_ and are not downloaded
+void AlignRunner::RunImpl(const AlignScoring& p, const PairView* pairs, int n, PairResult* out,
+                          std::vector<KeptTranscript>* keep)
+{
     const long long budget = std::max(1LL, env_ll("PBCCS_ALIGN_WORKSPACE_MB", 2048)) << 20;
     // host part: degenerate pairs, the work list
     std::vector<AlignJob> jobs;
@@ -525,7 +540,7 @@ void AlignRunner::Run(const AlignScoring& p, const PairView* pairs, int n, PairR
         std::memcpy(seq.data() + jobs[k].seqOff + pv.J, pv.query, (size_t)pv.I);
     }
 
-    std::vector<uint8_t> hOut((size_t)outBytes);
+    std::vector<uint8_t> hOut((size_t)(keep ? 0 : outBytes));
     std::vector<int> hLens(nj), hStatus(nj);
     std::vector<uint32_t> hScores(2 * (size_t)nj);
 
@@ -591,7 +606,8 @@ void AlignRunner::Run(const AlignScoring& p, const PairView* pairs, int n, PairR
         stats.bytes += (double)groups[q].bytes;
     }
 
-    check(hipMemcpyAsync(hOut.data(), dOut_.ptr, (size_t)outBytes, hipMemcpyDeviceToHost, stream_), "download");
+    if (!keep)
+        check(hipMemcpyAsync(hOut.data(), dOut_.ptr, (size_t)outBytes, hipMemcpyDeviceToHost, stream_), "download");
     check(hipMemcpyAsync(hLens.data(), dLens_.ptr, sizeof(int) * nj, hipMemcpyDeviceToHost, stream_), "download");
     check(hipMemcpyAsync(hStatus.data(), dStatus_.ptr, sizeof(int) * nj, hipMemcpyDeviceToHost, stream_), "download");
     check(hipMemcpyAsync(hScores.data(), dScores_.ptr, sizeof(uint32_t) * 2 * nj, hipMemcpyDeviceToHost, stream_),
@@ -617,6 +633,13 @@ void AlignRunner::Run(const AlignScoring& p, const PairView* pairs, int n, PairR
             continue;
         }
         stats.traceSteps += hLens[k];
+        if (keep) {
+            KeptTranscript& kt = (*keep)[pairOf[k]];
+            kt.onDevice = true;
+            kt.off = jb.outOff;
+            kt.len = hLens[k];
+            continue;
+        }
         const uint8_t* r = hOut.data() + jb.outOff;
         o.transcript.assign(reinterpret_cast<const char*>(r), (size_t)hLens[k]);
         std::reverse(o.transcript.begin(), o.transcript.end());

@@ -70,6 +70,14 @@ struct PairResult {
     int status = 0;   // PBCCS_OK / PBCCS_EINVAL / PBCCS_EOOM
 };
 
+// One pair whose transcript stays on the device (RunKeep): what the host may know of it.
+struct KeptTranscript {
+    int status = 0;        // PBCCS_OK / PBCCS_EINVAL / PBCCS_EOOM
+    bool onDevice = false; // false: a degenerate or refused pair, nothing of it is in TranscriptsDevice()
+    long long off = 0;     // the transcript, reversed (its last character first), in TranscriptsDevice()
+    int len = 0;
+};
+
 // The engine's align workspace: its own stream, the move store and the small per-call buffers.
 class AlignRunner {
 public:
@@ -83,10 +91,17 @@ public:
     // whose own store exceeds it gets status PBCCS_EOOM and no device work.
     void Run(const AlignScoring& p, const PairView* pairs, int n, PairResult* out);
 
+    // The same for a consumer on the device: no transcript leaves it, every transcript of the call stays in
+    // TranscriptsDevice() until the next call, and the host learns each pair's status, length and place.
+    void RunKeep(const AlignScoring& p, const PairView* pairs, int n, std::vector<KeptTranscript>* out);
+    const uint8_t* TranscriptsDevice() const { return dOut_.ptr; }
+
     AlignStats stats;
     bool profiling = false;
 
 private:
+    void RunImpl(const AlignScoring& p, const PairView* pairs, int n, PairResult* out,
+                 std::vector<KeptTranscript>* keep);
     int device_;
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};

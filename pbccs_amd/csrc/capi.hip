@@ -29,6 +29,7 @@
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
 #include "sparse_kernels.hpp"
+#include "window_kernels.hpp"
 
 using namespace pbccs;
 
@@ -115,6 +116,15 @@ struct pbccs_engine {
         if (!sparseRunner) sparseRunner.reset(new sparse::SparseRunner(device));
         sparseRunner->profiling = profiling;
         return *sparseRunner;
+    }
+    // the windowed polish's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<window::WindowRunner> windowRunner;
+    std::mutex windowMu;
+    pbccs_window_stats windowStats{};
+    window::WindowRunner& Window()
+    {
+        if (!windowRunner) windowRunner.reset(new window::WindowRunner(device));
+        return *windowRunner;
     }
     Workspace* Slot(int s)
     {
@@ -2426,6 +2436,555 @@ int pbccs_sparse_align_stats_get(pbccs_engine* eng, pbccs_sparse_align_stats* ou
     });
 }
 
+// ---- Windowed polish (window_kernels.hpp) ------------------------------------------------------
+void pbccs_window_options_default(pbccs_window_options* o)
+{
+    if (!o) return;
+    o->window = 2000;
+    o->overlap = 200;
+    o->guard = 8;
+    o->k = 6;
+}
+
+static bool window_options_ok(const pbccs_window_options* w)
+{
+    return w && w->window > w->overlap && w->guard >= 1 && (long long)w->overlap >= 2LL * w->guard &&
+           w->k >= sparse::kMinK && w->k <= sparse::kMaxK;
+}
+
+// Rule 1
+static std::vector<std::pair<int, int>> window_bounds(int L, const pbccs_window_options& w)
+{
+    std::vector<std::pair<int, int>> v;
+    if (L <= (long long)w.window + w.overlap) {
+        v.emplace_back(0, std::max(0, L));
+        return v;
+    }
+    const long long span = (long long)L - w.overlap;
+    const long long n = (span + w.window - 1) / w.window;
+    const long long S = (span + n - 1) / n;
+    for (long long i = 0; i < n; ++i)
+        v.emplace_back((int)(i * S), (int)std::min<long long>(L, i * S + S + w.overlap));
+    return v;
+}
+
+int pbccs_window_plan(int draft_len, const pbccs_window_options* w, int* bounds, int cap, int* n_windows)
+{
+    if (!window_options_ok(w)) return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
+    if (draft_len < 0 || !n_windows || cap < 0 || (cap > 0 && !bounds)) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        const std::vector<std::pair<int, int>> v = window_bounds(draft_len, *w);
+        *n_windows = (int)v.size();
+        if ((int)v.size() > cap) return fail(PBCCS_ERANGE, "bounds buffer too small");
+        for (size_t i = 0; i < v.size(); ++i) bounds[2 * i] = v[i].first, bounds[2 * i + 1] = v[i].second;
+        return PBCCS_OK;
+    });
+}
+
+// Rule 4 on one transcript: per draft column the index of its character, and TargetToQueryPositions.
+static bool window_columns(const char* t, int len, int width, std::vector<int>* col, std::vector<int>* ttq)
+{
+    col->clear();
+    ttq->clear();
+    int q = 0;
+    for (int x = 0; x < len; ++x) {
+        const char c = t[x];
+        if (c == 'M' || c == 'R') col->push_back(x), ttq->push_back(q++);
+        else if (c == 'D') col->push_back(x), ttq->push_back(q);
+        else if (c == 'I') ++q;
+        else return false;
+    }
+    ttq->push_back(q);
+    return (int)col->size() == width;
+}
+
+static bool window_good_at(const char* t, int len, const std::vector<int>& col, int rel, int g)
+{
+    if (rel - g < 0 || rel + g > (int)col.size()) return false;
+    const int x0 = col[rel - g];
+    if (x0 + 2 * g > len) return false;
+    for (int x = x0; x < x0 + 2 * g; ++x)
+        if (t[x] != 'M') return false;
+    return true;
+}
+
+int pbccs_window_join(const char* transcript_a, int len_a, int begin_a, int end_a, const char* transcript_b,
+                      int len_b, int begin_b, int end_b, int guard, int* found, int* p, int* cut_a, int* cut_b)
+{
+    if (len_a < 0 || len_b < 0 || (len_a > 0 && !transcript_a) || (len_b > 0 && !transcript_b) || guard < 1 || !found ||
+        !p || !cut_a || !cut_b || begin_a < 0 || begin_a > end_a || begin_b > end_b || begin_a >= begin_b)
+        return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<int> colA, colB, ttqA, ttqB;
+        if (!window_columns(transcript_a, len_a, end_a - begin_a, &colA, &ttqA) ||
+            !window_columns(transcript_b, len_b, end_b - begin_b, &colB, &ttqB))
+            return fail(PBCCS_EINVAL, "a transcript does not span its window or holds a character other than M R I D");
+        *found = 0;
+        *p = -1;
+        *cut_a = *cut_b = 0;
+        const long long lo = (long long)begin_b + guard, hi = (long long)end_a - guard;
+        if (lo > hi) return PBCCS_OK;
+        const long long mid = ((long long)begin_b + end_a) / 2;
+        for (long long d = 0; mid - d >= lo || mid + d <= hi; ++d) {
+            for (int side = 0; side < (d == 0 ? 1 : 2); ++side) {
+                const long long c = side == 0 ? mid + d : mid - d;
+                if (c < lo || c > hi || c - begin_b > end_b - begin_b) continue;
+                const int ra = (int)(c - begin_a), rb = (int)(c - begin_b);
+                if (!window_good_at(transcript_a, len_a, colA, ra, guard) ||
+                    !window_good_at(transcript_b, len_b, colB, rb, guard))
+                    continue;
+                *found = 1;
+                *p = (int)c;
+                *cut_a = ttqA[ra];
+                *cut_b = ttqB[rb];
+                return PBCCS_OK;
+            }
+        }
+        return PBCCS_OK;
+    });
+}
+
+struct WinSlice {
+    int cb, ce, ts, te;   // cb < 0: a placeholder
+};
+struct WinZmw {
+    std::vector<std::pair<int, int>> wins;
+    std::vector<WinSlice> sl;   // [window * n_reads + read]
+    int unanchored = 0;
+};
+
+static int window_check_inputs(const pbccs_zmw_input* in, int n)
+{
+    for (int z = 0; z < n; ++z) {
+        const pbccs_zmw_input& s = in[z];
+        if (s.draft_len < 0 || (s.draft_len > 0 && !s.draft) ||
+            (s.n_reads > 0 && (!s.seqs || !s.lens || !s.strands || !s.tstarts || !s.tends)))
+            return fail(PBCCS_EINVAL, "bad pbccs_zmw_input");
+    }
+    return PBCCS_OK;
+}
+
+// Rules 1 and 2 for every ZMW: the plan, the chains (kept on the device) and the cuts (k_window_cuts).
+static void window_slices_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_window_options& w,
+                               int minLength, std::vector<WinZmw>* out)
+{
+    out->assign((size_t)n, WinZmw());
+    struct JobRef {
+        int z, r;
+    };
+    std::vector<sparse::SparseInput> jobs;
+    std::vector<JobRef> refs;
+    for (int z = 0; z < n; ++z) {
+        const pbccs_zmw_input& s = in[z];
+        WinZmw& Z = (*out)[z];
+        Z.wins = window_bounds(s.draft_len, w);
+        const int nr = std::max(0, s.n_reads), nw = (int)Z.wins.size();
+        Z.sl.assign((size_t)nw * nr, WinSlice{-1, -1, -1, -1});
+        for (int r = 0; r < nr; ++r) {
+            if (!s.seqs[r]) continue;
+            const bool mapped = s.tstarts[r] >= 0 && s.tends[r] <= s.draft_len && s.tstarts[r] < s.tends[r] && s.lens[r] > 0;
+            if (nw == 1 || !mapped) {   // as it is; a read the driver would refuse stays refused in window 0
+                Z.sl[r] = WinSlice{0, std::max(0, s.lens[r]), s.tstarts[r], s.tends[r]};
+                continue;
+            }
+            jobs.push_back(sparse::SparseInput{s.draft + s.tstarts[r], s.tends[r] - s.tstarts[r], s.seqs[r], s.lens[r],
+                                               s.strands[r] ? 1 : 0, nullptr, 0, nullptr});
+            refs.push_back(JobRef{z, r});
+        }
+    }
+    if (jobs.empty()) return;
+    std::lock_guard<std::mutex> lk(eng->sparseMu);   // the chains stay the runner's until the cuts are taken
+    std::vector<sparse::KeptChain> kept;
+    eng->Sparse().RunKeep(w.k, jobs.data(), (int)jobs.size(), &kept);
+    struct Pending {
+        int z, w, r, iLo, iHi, lo, hi;   // iLo / iHi: a cut task, -1 the read's start, -2 its end
+    };
+    std::vector<window::CutTask> tasks;
+    std::vector<Pending> pend;
+    for (size_t g = 0; g < jobs.size(); ++g) {
+        const int z = refs[g].z, r = refs[g].r;
+        WinZmw& Z = (*out)[z];
+        if (kept[g].status != PBCCS_OK || kept[g].nAnchors <= 0) {
+            Z.unanchored++;
+            continue;
+        }
+        const int ts = in[z].tstarts[r], te = in[z].tends[r], flen = in[z].lens[r];
+        auto boundary = [&](int b) {
+            if (b == ts) return -1;
+            if (b == te) return -2;
+            tasks.push_back(window::CutTask{kept[g].anchorOff, kept[g].nAnchors, b - ts, flen});
+            return (int)tasks.size() - 1;
+        };
+        for (int x = 0; x < (int)Z.wins.size(); ++x) {
+            const int lo = std::max(ts, Z.wins[x].first), hi = std::min(te, Z.wins[x].second);
+            if (hi - lo < minLength || hi <= lo) continue;
+            const int iLo = boundary(lo), iHi = boundary(hi);
+            pend.push_back(Pending{z, x, r, iLo, iHi, lo, hi});
+        }
+    }
+    std::vector<int> cuts;
+    {
+        std::lock_guard<std::mutex> wl(eng->windowMu);
+        eng->Window().Cuts(eng->Sparse().AnchorsDevice(), tasks, &cuts);
+        eng->windowStats.cut_tasks += (long long)tasks.size();
+        eng->windowStats.launches += tasks.empty() ? 0 : 1;
+    }
+    for (const Pending& p : pend) {
+        const int flen = in[p.z].lens[p.r];
+        const int cb = p.iLo == -1 ? 0 : (p.iLo == -2 ? flen : cuts[p.iLo]);
+        const int ce = p.iHi == -1 ? 0 : (p.iHi == -2 ? flen : cuts[p.iHi]);
+        if (ce - cb < minLength || ce <= cb) continue;
+        WinZmw& Z = (*out)[p.z];
+        Z.sl[(size_t)p.w * in[p.z].n_reads + p.r] = WinSlice{cb, ce, p.lo - Z.wins[p.w].first, p.hi - Z.wins[p.w].first};
+    }
+}
+
+int pbccs_window_slices(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_window_options* w,
+                        int min_length, int* n_windows, int* slices, long long cap, long long* n_ints,
+                        int* unanchored)
+{
+    if (!window_options_ok(w)) return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
+    if (!eng || n < 0 || (n > 0 && (!in || !n_windows)) || !n_ints || cap < 0 || (cap > 0 && !slices))
+        return fail(PBCCS_EINVAL, "bad argument");
+    if (window_check_inputs(in, n) != PBCCS_OK) return PBCCS_EINVAL;
+    return guarded([&] {
+        long long need = 0;
+        for (int z = 0; z < n; ++z) {
+            n_windows[z] = (int)window_bounds(in[z].draft_len, *w).size();
+            need += 4LL * n_windows[z] * std::max(0, in[z].n_reads);
+        }
+        *n_ints = need;
+        if (need > cap) return fail(PBCCS_ERANGE, "slices buffer too small");
+        if (hipSetDevice(eng->device) != hipSuccess) return fail(PBCCS_EDEVICE, "hipSetDevice failed");
+        std::vector<WinZmw> Z;
+        window_slices_impl(eng, in, n, *w, min_length, &Z);
+        long long at = 0;
+        for (int z = 0; z < n; ++z) {
+            for (const WinSlice& s : Z[z].sl) {
+                slices[at++] = s.cb, slices[at++] = s.ce;
+                slices[at++] = s.cb < 0 ? -1 : s.ts, slices[at++] = s.cb < 0 ? -1 : s.te;
+            }
+            if (unanchored) unanchored[z] = Z[z].unanchored;
+        }
+        return PBCCS_OK;
+    });
+}
+
+// One window (or one single-window ZMW) of the first pbccs_polish_batch call: what its input and output point into.
+struct WinBuf {
+    std::vector<const char*> seqs;
+    std::vector<int> lens, ts, te, arr, qvs;
+    std::vector<double> zsc;
+    std::vector<char> cons;
+};
+
+static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options& o,
+                                const pbccs_window_options& w, pbccs_zmw_output* out, pbccs_window_info* info)
+{
+    using Clock = std::chrono::steady_clock;
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (hipSetDevice(eng->device) != hipSuccess) return fail(PBCCS_EDEVICE, "hipSetDevice failed");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const auto t0 = Clock::now();
+    std::vector<WinZmw> Z;
+    window_slices_impl(eng, in, n, w, o.min_length, &Z);
+    const auto t1 = Clock::now();
+
+    // rule 3: every window of every multi-window ZMW, and every one-window ZMW as it is, in one call
+    std::vector<int> first((size_t)n + 1, 0);
+    for (int z = 0; z < n; ++z) first[z + 1] = first[z] + (int)Z[z].wins.size();
+    const int np = first[n];
+    std::vector<pbccs_zmw_input> pin((size_t)np);
+    std::vector<pbccs_zmw_output> pout((size_t)np);
+    std::vector<WinBuf> buf((size_t)np);
+    long long multi = 0, windows = 0, unanchored = 0;
+    for (int z = 0; z < n; ++z) {
+        const int nw = (int)Z[z].wins.size(), nr = std::max(0, in[z].n_reads);
+        if (nw == 1) {
+            pin[first[z]] = in[z];
+            pout[first[z]] = out[z];
+            continue;
+        }
+        ++multi;
+        windows += nw;
+        unanchored += Z[z].unanchored;
+        for (int x = 0; x < nw; ++x) {
+            WinBuf& B = buf[first[z] + x];
+            const int s = Z[z].wins[x].first, e = Z[z].wins[x].second;
+            B.seqs.assign((size_t)nr, nullptr);
+            B.lens.assign((size_t)nr, 0);
+            B.ts.assign((size_t)nr, 0);
+            B.te.assign((size_t)nr, e - s);
+            B.arr.assign((size_t)nr, -1);
+            B.zsc.assign((size_t)nr, nan);
+            B.cons.assign(2 * (size_t)(e - s) + 64, 0);
+            B.qvs.assign(B.cons.size(), 0);
+            for (int r = 0; r < nr; ++r) {
+                const WinSlice& sl = Z[z].sl[(size_t)x * nr + r];
+                if (sl.cb < 0) continue;
+                // as sequenced: the reverse strand's slice is seq[|f| - end, |f| - begin)
+                B.seqs[r] = in[z].seqs[r] + (in[z].strands[r] ? in[z].lens[r] - sl.ce : sl.cb);
+                B.lens[r] = sl.ce - sl.cb;
+                B.ts[r] = sl.ts;
+                B.te[r] = sl.te;
+            }
+            pbccs_zmw_input& pi = pin[first[z] + x];
+            pi = in[z];
+            pi.draft = in[z].draft + s;
+            pi.draft_len = e - s;
+            pi.seqs = B.seqs.data();
+            pi.lens = B.lens.data();
+            pi.tstarts = B.ts.data();
+            pi.tends = B.te.data();
+            pbccs_zmw_output& po = pout[first[z] + x];
+            std::memset(&po, 0, sizeof(po));
+            po.consensus = B.cons.data();
+            po.consensus_cap = (int)B.cons.size();
+            po.qvs = B.qvs.data();
+            po.add_read_results = B.arr.data();
+            po.zscores = B.zsc.data();
+        }
+    }
+    int rc = pbccs_polish_batch(eng, pin.data(), np, &o, pout.data());
+    if (rc != PBCCS_OK) return rc;
+    const auto t2 = Clock::now();
+
+    // rule 4: the joins of the ZMWs whose windows all succeeded
+    std::vector<char> whole((size_t)n, 0);   // the fallback reason per ZMW
+    std::vector<align::PairView> pairs;
+    std::vector<int> pairOf((size_t)np, -1);
+    for (int z = 0; z < n; ++z) {
+        const int nw = (int)Z[z].wins.size();
+        if (nw == 1) continue;
+        for (int x = 0; x < nw; ++x)
+            if (pout[first[z] + x].status != PBCCS_ZMW_SUCCESS) whole[z] = PBCCS_WINDOW_FALLBACK_WINDOW;
+        if (whole[z]) continue;
+        for (int x = 0; x < nw; ++x) {
+            pairOf[first[z] + x] = (int)pairs.size();
+            pairs.push_back(align::PairView{pin[first[z] + x].draft, pin[first[z] + x].draft_len, pout[first[z] + x].consensus,
+                                            pout[first[z] + x].consensus_len});
+        }
+    }
+    struct JointRef {
+        int z, x;
+    };
+    std::vector<JointRef> jref;
+    std::vector<window::JoinOut> joins;
+    if (!pairs.empty()) {
+        const align::AlignScoring sc{align::kNw, 0, -1, -1, -1, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const char* hj = std::getenv("PBCCS_WINDOW_HOST_JOIN");   // tests: the host rule on downloaded transcripts
+        const bool hostJoin = hj && hj[0] == '1';
+        std::lock_guard<std::mutex> lk(eng->alignMu);   // the transcripts stay the runner's until the joins are taken
+        std::vector<align::KeptTranscript> kept;
+        std::vector<align::PairResult> full;
+        if (hostJoin) {
+            full.resize(pairs.size());
+            eng->Align().Run(sc, pairs.data(), (int)pairs.size(), full.data());
+        } else {
+            eng->Align().RunKeep(sc, pairs.data(), (int)pairs.size(), &kept);
+        }
+        std::vector<window::JoinTask> tasks;
+        std::vector<int> taskOf;
+        for (int z = 0; z < n; ++z) {
+            const int nw = (int)Z[z].wins.size();
+            if (nw == 1 || whole[z]) continue;
+            for (int x = 0; x + 1 < nw; ++x) {
+                jref.push_back(JointRef{z, x});
+                joins.push_back(window::JoinOut{-1, 0, 0});
+                const int a = pairOf[first[z] + x], b = pairOf[first[z] + x + 1];
+                const std::pair<int, int> wa = Z[z].wins[x], wb = Z[z].wins[x + 1];
+                if (hostJoin) {
+                    int found = 0, p = -1, ca = 0, cb = 0;
+                    if (full[a].status == PBCCS_OK && full[b].status == PBCCS_OK && wa.first < wb.first &&
+                        pbccs_window_join(full[a].transcript.data(), (int)full[a].transcript.size(), wa.first, wa.second,
+                                          full[b].transcript.data(), (int)full[b].transcript.size(), wb.first, wb.second,
+                                          w.guard, &found, &p, &ca, &cb) == PBCCS_OK &&
+                        found)
+                        joins.back() = window::JoinOut{p, ca, cb};
+                    continue;
+                }
+                if (!kept[a].onDevice || !kept[b].onDevice || kept[a].status != PBCCS_OK || kept[b].status != PBCCS_OK)
+                    continue;
+                window::JoinTask t;
+                t.offA = kept[a].off, t.offB = kept[b].off, t.workOff = 0;
+                t.lenA = kept[a].len, t.lenB = kept[b].len;
+                t.sA = wa.first, t.sB = wb.first;
+                t.lo = wb.first + w.guard, t.hi = wa.second - w.guard, t.mid = (wb.first + wa.second) / 2;
+                t.guard = w.guard;
+                if (t.lo > t.hi) continue;
+                taskOf.push_back((int)joins.size() - 1);
+                tasks.push_back(t);
+            }
+        }
+        if (!tasks.empty()) {
+            std::vector<window::JoinOut> got;
+            std::lock_guard<std::mutex> wl(eng->windowMu);
+            eng->Window().Joins(eng->Align().TranscriptsDevice(), tasks, &got);
+            for (size_t q = 0; q < tasks.size(); ++q) joins[taskOf[q]] = got[q];
+            eng->windowStats.launches += 1;
+        }
+    }
+    const auto t3 = Clock::now();
+
+    // rules 5 and 6: stitch, or send the ZMW to the whole-template route
+    std::vector<std::vector<pbccs_window_record>> recs((size_t)n);
+    for (int z = 0; z < n; ++z) {
+        const int nw = (int)Z[z].wins.size();
+        recs[z].resize((size_t)nw);
+        for (int x = 0; x < nw; ++x) {
+            const pbccs_zmw_output& po = pout[first[z] + x];
+            recs[z][x] = pbccs_window_record{Z[z].wins[x].first, Z[z].wins[x].second, -1, 0, 0, po.status, po.n_tested, po.n_applied};
+        }
+        if (nw == 1) {
+            out[z] = pout[first[z]];
+            recs[z][0].cut_end = std::max(0, out[z].consensus_len);
+        }
+    }
+    for (size_t q = 0; q < jref.size();) {
+        const int z = jref[q].z, nw = (int)Z[z].wins.size();
+        int begin = 0;
+        for (int x = 0; x + 1 < nw; ++x, ++q) {
+            if (whole[z]) continue;
+            const window::JoinOut& j = joins[q];
+            if (j.p < 0 || j.cutA < begin || j.cutA > pout[first[z] + x].consensus_len ||
+                j.cutB > pout[first[z] + x + 1].consensus_len) {
+                whole[z] = PBCCS_WINDOW_FALLBACK_NO_JOIN;
+                continue;
+            }
+            recs[z][x].join = j.p;
+            recs[z][x].cut_begin = begin;
+            recs[z][x].cut_end = j.cutA;
+            begin = j.cutB;
+        }
+        if (!whole[z]) {
+            recs[z][nw - 1].cut_begin = begin;
+            recs[z][nw - 1].cut_end = pout[first[z] + nw - 1].consensus_len;
+        }
+    }
+    for (int z = 0; z < n; ++z) {
+        const int nw = (int)Z[z].wins.size(), nr = std::max(0, in[z].n_reads);
+        if (nw == 1 || whole[z]) continue;
+        long long len = 0;
+        double err = 0.0;
+        for (int x = 0; x < nw; ++x) {
+            const pbccs_window_record& R = recs[z][x];
+            len += R.cut_end - R.cut_begin;
+            for (int c = R.cut_begin; c < R.cut_end; ++c)
+                err += std::pow(10.0, static_cast<double>(pout[first[z] + x].qvs[c]) / -10.0);
+        }
+        const double acc = len > 0 ? 1.0 - err / (double)len : 0.0;
+        if (len <= 0 || acc < o.min_predicted_accuracy) {
+            whole[z] = PBCCS_WINDOW_FALLBACK_ACCURACY;
+            continue;
+        }
+        pbccs_zmw_output& q = out[z];
+        q.predicted_accuracy = acc;
+        q.n_tested = q.n_applied = 0;
+        q.n_passes = 0;
+        q.zg = nan;
+        for (int c = 0; c < 5; ++c) q.status_counts[c] = 0;
+        for (int x = 0; x < nw; ++x) {
+            const pbccs_zmw_output& po = pout[first[z] + x];
+            q.n_tested += po.n_tested;
+            q.n_applied += po.n_applied;
+            if (!(po.zg >= q.zg)) q.zg = po.zg;   // the minimum; a NaN zg stays
+        }
+        double zsum = 0.0;
+        int zn = 0;
+        for (int r = 0; r < nr; ++r) {
+            int code = -1;
+            double zmin = nan;
+            for (int x = 0; x < nw; ++x) {
+                const int c = buf[first[z] + x].arr[r];
+                if (c >= 0 && (code < 0 || code == PBCCS_ADD_SUCCESS)) code = c;
+                const double v = buf[first[z] + x].zsc[r];
+                if (!std::isnan(v) && !(v >= zmin)) zmin = v;
+            }
+            if (q.add_read_results) q.add_read_results[r] = code;
+            if (q.zscores) q.zscores[r] = zmin;
+            if (code >= 0) q.status_counts[code] += 1;
+            if (code == PBCCS_ADD_SUCCESS) {
+                if (!in[z].full_pass || in[z].full_pass[r]) q.n_passes += 1;
+                if (!std::isnan(zmin)) zsum += zmin, ++zn;
+            }
+        }
+        q.za = zn ? zsum / zn : nan;
+        if (len + 1 > q.consensus_cap || !q.consensus) {
+            q.consensus_len = -(int)len;
+            q.status = PBCCS_ZMW_OTHER;
+            continue;
+        }
+        long long at = 0;
+        for (int x = 0; x < nw; ++x) {
+            const pbccs_window_record& R = recs[z][x];
+            const int m = R.cut_end - R.cut_begin;
+            std::memcpy(q.consensus + at, pout[first[z] + x].consensus + R.cut_begin, (size_t)m);
+            if (q.qvs) std::copy(pout[first[z] + x].qvs + R.cut_begin, pout[first[z] + x].qvs + R.cut_end, q.qvs + at);
+            at += m;
+        }
+        q.consensus[at] = 0;
+        q.consensus_len = (int)len;
+        q.status = PBCCS_ZMW_SUCCESS;
+    }
+
+    // the fallbacks of the call, whole, in a second call
+    std::vector<int> fz;
+    for (int z = 0; z < n; ++z)
+        if (whole[z]) fz.push_back(z);
+    if (!fz.empty()) {
+        std::vector<pbccs_zmw_input> fin;
+        std::vector<pbccs_zmw_output> fout;
+        for (int z : fz) fin.push_back(in[z]), fout.push_back(out[z]);
+        rc = pbccs_polish_batch(eng, fin.data(), (int)fz.size(), &o, fout.data());
+        if (rc != PBCCS_OK) return rc;
+        for (size_t q = 0; q < fz.size(); ++q) out[fz[q]] = fout[q];
+    }
+    const auto t4 = Clock::now();
+    if (info)
+        for (int z = 0; z < n; ++z) {
+            info[z].n_windows = (int)Z[z].wins.size();
+            info[z].fallback = whole[z];
+            info[z].unanchored_reads = Z[z].unanchored;
+            if (info[z].windows)
+                for (int x = 0; x < std::min(info[z].n_windows, info[z].windows_cap); ++x) info[z].windows[x] = recs[z][x];
+        }
+    {
+        std::lock_guard<std::mutex> wl(eng->windowMu);
+        pbccs_window_stats& S = eng->windowStats;
+        S.zmws += multi;
+        S.windows += windows;
+        S.unanchored_reads += unanchored;
+        S.joints += (long long)jref.size();
+        for (int z : fz) S.fallbacks[(int)whole[z]] += 1;
+        S.slices_ms += ms(t0, t1);
+        S.polish_ms += ms(t1, t2);
+        S.join_ms += ms(t2, t3);
+        S.fallback_ms += ms(t3, t4);
+    }
+    return PBCCS_OK;
+}
+
+int pbccs_polish_windowed(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                          const pbccs_window_options* w, pbccs_zmw_output* out, pbccs_window_info* info)
+{
+    if (!window_options_ok(w)) return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    if (window_check_inputs(in, n) != PBCCS_OK) return PBCCS_EINVAL;
+    pbccs_polish_options o;
+    if (opts) o = *opts;
+    else pbccs_polish_options_default(&o);
+    return guarded([&] { return polish_windowed_impl(eng, in, n, o, *w, out, info); });
+}
+
+int pbccs_window_stats_get(pbccs_engine* eng, pbccs_window_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lk(eng->windowMu);
+    *out = eng->windowStats;
+    if (reset) eng->windowStats = pbccs_window_stats{};
+    return PBCCS_OK;
+}
+
 // One POA chunk of the pipelined ccs batch: its live ZMWs and everything their polish inputs point into.
 struct CcsChunk {
     std::vector<int> zs;   // caller indices of the chunk's ZMWs
@@ -2577,9 +3136,14 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
 }
 
 static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
-                          bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out)
+                          bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out,
+                          const pbccs_window_options* win = nullptr, pbccs_window_info* info = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
+    if (win && !window_options_ok(win))
+        return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
+    if (win && info)
+        for (int z = 0; z < n; ++z) info[z].n_windows = info[z].fallback = info[z].unanchored_reads = 0;
     pbccs_polish_options o;
     if (opts) o = *opts;
     else pbccs_polish_options_default(&o);
@@ -2725,7 +3289,9 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
         };
         // PBCCS_CCS_SERIAL=1: every chunk drafted before the first polishes (the A/B reference schedule)
         const char* serialEnv = std::getenv("PBCCS_CCS_SERIAL");
-        const bool serial = serialEnv && serialEnv[0] == '1';
+        // windows: the windowed polish runs pbccs_polish_batch on every slot itself, so the chunks polish one after
+        // another once all are drafted
+        const bool serial = win || (serialEnv && serialEnv[0] == '1');
         std::vector<std::thread> pool;
         if (!serial)
             for (int s = 0; s < std::min(slots, nb); ++s) pool.emplace_back(worker, s);
@@ -2771,7 +3337,22 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
         }
         if (serial) {
             for (poa::PoaRunner* r : eng->PoaRunners()) r->ReleasePool();
-            for (int s = 0; s < std::min(slots, nb); ++s) pool.emplace_back(worker, s);
+            if (!win)
+                for (int s = 0; s < std::min(slots, nb); ++s) pool.emplace_back(worker, s);
+        }
+        if (win && rcDraft == PBCCS_OK) {
+            for (int c = 0; c < nb && rcDraft == PBCCS_OK; ++c) {
+                CcsChunk& C = chunks[c];
+                const int m = (int)C.pin.size();
+                if (m == 0) continue;
+                std::vector<pbccs_window_info> cinfo;
+                if (info)
+                    for (int q = 0; q < m; ++q) cinfo.push_back(info[C.pinZ[q]]);
+                rcDraft = polish_windowed_impl(eng, C.pin.data(), m, o, *win, C.pout.data(), info ? cinfo.data() : nullptr);
+                if (rcDraft != PBCCS_OK) errDraft = g_lastError;
+                else if (info)
+                    for (int q = 0; q < m; ++q) info[C.pinZ[q]] = cinfo[q];
+            }
         }
         for (std::thread& t : pool) t.join();
         for (int s = 0; s < slots; ++s) eng->Slot(s)->TrimRetired();   // every chunk's batch is destroyed
@@ -2851,6 +3432,17 @@ int pbccs_ccs_batch_ex2(pbccs_engine* eng, const pbccs_ccs_input* in, int n, con
     if (ccs) c = *ccs;
     else pbccs_ccs_options_default(&c);
     return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out);
+}
+
+int pbccs_ccs_batch_ex3(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_window_options* win,
+                        const pbccs_polish_options* opts, pbccs_ccs_output* out, pbccs_window_info* info)
+{
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out, win,
+                          info);
 }
 
 }  // extern "C"

@@ -184,7 +184,8 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
     return out
 
 
-def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False):
+def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
+              polish_window=None):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -197,6 +198,10 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     (mapping.map_to_draft's aligner) and reach AddRead like the POA's reads, in FilterReads' order.
     banded_poa (pbccs_ccs_batch_ex2): the draft's alignments are filled inside SdpRangeFinder's ranges
     (poa.poa_batch(banded=True)); everything after the draft is unchanged.
+    polish_window (pbccs_ccs_batch_ex3): None, or the windowed polish's options as a dict with any of window,
+    overlap, guard, k (polish.polish_windowed's defaults for the rest): drafts longer than window + overlap are
+    polished in overlapping windows and stitched.  The results then also carry "n_windows", "windowed" and
+    "fallback" (polish.WINDOW_FALLBACK names the codes).
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -257,7 +262,17 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         outs["add_order"][:n] = order.ctypes.data + 4 * f0
     opts = settings._c()
     mc = 2**62 if max_poa_coverage is None else int(max_poa_coverage)
-    if banded_poa:
+    winfo = None
+    if polish_window is not None:
+        from .polish import window_options
+        wo = window_options(**dict(polish_window))
+        winfo = (L.CWindowInfo * max(1, n))()
+        co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
+        po = L.CPoaOptions(mc, -1, 1 if banded_poa else 0)
+        L.check(L.load().pbccs_ccs_batch_ex3(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                             ctypes.byref(co), ctypes.byref(po), ctypes.byref(wo), ctypes.byref(opts),
+                                             ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput)), winfo))
+    elif banded_poa:
         co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
         po = L.CPoaOptions(mc, -1, 1)
         L.check(L.load().pbccs_ccs_batch_ex2(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
@@ -294,4 +309,6 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
                     "add_order": [k for k in order_l[f:f + nr] if k >= 0],
                     "zg": zg[z], "za": za[z], "predicted_accuracy": pacc[z], "n_tested": ntest[z],
                     "n_applied": nappl[z], "n_passes": npass[z], "status_counts": scounts[z]})
+        if winfo is not None:
+            res[-1].update(n_windows=winfo[z].n_windows, windowed=winfo[z].n_windows > 1, fallback=winfo[z].fallback)
     return res

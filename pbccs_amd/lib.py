@@ -231,6 +231,28 @@ class CSparseAlignStats(ctypes.Structure):
                 ("range_cells", ctypes.c_longlong), ("full_cells", ctypes.c_longlong)]
 
 
+class CWindowOptions(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_int), ("overlap", ctypes.c_int), ("guard", ctypes.c_int), ("k", ctypes.c_int)]
+
+
+class CWindowRecord(ctypes.Structure):
+    _fields_ = [("begin", ctypes.c_int), ("end", ctypes.c_int), ("join", ctypes.c_int), ("cut_begin", ctypes.c_int),
+                ("cut_end", ctypes.c_int), ("status", ctypes.c_int), ("n_tested", ctypes.c_longlong),
+                ("n_applied", ctypes.c_longlong)]
+
+
+class CWindowInfo(ctypes.Structure):
+    _fields_ = [("n_windows", ctypes.c_int), ("fallback", ctypes.c_int), ("unanchored_reads", ctypes.c_int),
+                ("windows", ctypes.POINTER(CWindowRecord)), ("windows_cap", ctypes.c_int)]
+
+
+class CWindowStats(ctypes.Structure):
+    _fields_ = [("zmws", ctypes.c_longlong), ("windows", ctypes.c_longlong), ("fallbacks", ctypes.c_longlong * 4),
+                ("unanchored_reads", ctypes.c_longlong), ("cut_tasks", ctypes.c_longlong),
+                ("joints", ctypes.c_longlong), ("launches", ctypes.c_longlong), ("slices_ms", ctypes.c_double),
+                ("polish_ms", ctypes.c_double), ("join_ms", ctypes.c_double), ("fallback_ms", ctypes.c_double)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -356,12 +378,26 @@ SIGNATURES = {
     "pbccs_sparse_poa_alignable_ranges": (I, [P, ctypes.c_char_p, I, I, PI, I, PI, PI, I, PI, PI, I, PI, PI]),
     "pbccs_sparse_poa_try_add_read": (I, [P, ctypes.c_char_p, I, I, I, PF, PI, I, PI]),
     "pbccs_poa_band_stats_get": (I, [P, ctypes.POINTER(CPoaBandStats), I]),
+    # windowed polish
+    "pbccs_window_options_default": (None, [ctypes.POINTER(CWindowOptions)]),
+    "pbccs_window_plan": (I, [I, ctypes.POINTER(CWindowOptions), PI, I, PI]),
+    "pbccs_window_join": (I, [ctypes.c_char_p, I, I, I, ctypes.c_char_p, I, I, I, I, PI, PI, PI, PI]),
+    "pbccs_window_slices": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CWindowOptions), I, PI, PI,
+                                ctypes.c_longlong, PLL, PI]),
+    "pbccs_polish_windowed": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
+                                  ctypes.POINTER(CWindowOptions), ctypes.POINTER(CZmwOutput),
+                                  ctypes.POINTER(CWindowInfo)]),
+    "pbccs_window_stats_get": (I, [P, ctypes.POINTER(CWindowStats), I]),
 }
 # bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
 DIGIT_SIGNATURES = {
     "pbccs_ccs_batch_ex2": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
                                 ctypes.POINTER(CPoaOptions), ctypes.POINTER(CPolishOptions),
                                 ctypes.POINTER(CCcsOutput)]),
+    "pbccs_ccs_batch_ex3": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                                ctypes.POINTER(CPoaOptions), ctypes.POINTER(CWindowOptions),
+                                ctypes.POINTER(CPolishOptions), ctypes.POINTER(CCcsOutput),
+                                ctypes.POINTER(CWindowInfo)]),
 }
 
 

@@ -161,6 +161,116 @@ def polish_zmws(zmws, settings=None, engine=None):
         b.close()
 
 
+WINDOW_FALLBACK = {0: None, 1: "window status", 2: "no join", 3: "predicted accuracy"}
+
+
+def window_options(window=2000, overlap=200, guard=8, k=6):
+    """pbccs_window_options; ValueError unless window > overlap >= 2 guard, guard >= 1 and 4 <= k <= 8."""
+    window, overlap, guard, k = int(window), int(overlap), int(guard), int(k)
+    if not (window > overlap and overlap >= 2 * guard and guard >= 1 and 4 <= k <= 8):
+        raise ValueError("window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8")
+    return L.CWindowOptions(window, overlap, guard, k)
+
+
+def window_plan(draft_len, window=2000, overlap=200):
+    """The windows [(begin, end)] of a draft (pbccs_window_plan; host only, no device)."""
+    wo = L.CWindowOptions(int(window), int(overlap), 1, 8)
+    nw = ctypes.c_int()
+    rc = L.load().pbccs_window_plan(int(draft_len), ctypes.byref(wo), None, 0, ctypes.byref(nw))
+    if rc not in (L.PBCCS_OK, -5):
+        L.check(rc)
+    b = (ctypes.c_int * (2 * max(1, nw.value)))()
+    L.check(L.load().pbccs_window_plan(int(draft_len), ctypes.byref(wo), b, nw.value, ctypes.byref(nw)))
+    return [(b[2 * i], b[2 * i + 1]) for i in range(nw.value)]
+
+
+def window_join(transcript_a, bounds_a, transcript_b, bounds_b, guard=8):
+    """The join of two neighbouring windows from their draft-to-consensus transcripts (pbccs_window_join; host
+    only): (p, cut_a, cut_b), or None when no candidate has 2 guard neighbouring M around it in both."""
+    found, p, ca, cb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    ta, tb = transcript_a.encode(), transcript_b.encode()
+    L.check(L.load().pbccs_window_join(ta, len(ta), int(bounds_a[0]), int(bounds_a[1]), tb, len(tb), int(bounds_b[0]),
+                                       int(bounds_b[1]), int(guard), ctypes.byref(found), ctypes.byref(p),
+                                       ctypes.byref(ca), ctypes.byref(cb)))
+    return (p.value, ca.value, cb.value) if found.value else None
+
+
+def window_slices(zmws, window=2000, overlap=200, k=6, min_length=10, engine=None):
+    """Where every read is cut at the window boundaries (pbccs_window_slices; the chains and the cuts run on the
+    GPU).  Per ZMW: {"windows": [(begin, end)], "slices": per window a list with one entry per read -- None for a
+    placeholder, else (begin, end, ts', te') with [begin, end) in the read's forward text --, "unanchored_reads"}."""
+    from . import default_engine
+    engine = engine or default_engine()
+    wo = L.CWindowOptions(int(window), int(overlap), 1, int(k))
+    m = _Marshalled(zmws)
+    n = len(zmws)
+    nw = (ctypes.c_int * max(1, n))()
+    un = (ctypes.c_int * max(1, n))()
+    need = ctypes.c_longlong()
+    rc = L.load().pbccs_window_slices(engine._h, m._ins, n, ctypes.byref(wo), int(min_length), nw, None, 0,
+                                      ctypes.byref(need), un)
+    if rc not in (L.PBCCS_OK, -5):
+        L.check(rc)
+    buf = (ctypes.c_int * max(1, need.value))()
+    L.check(L.load().pbccs_window_slices(engine._h, m._ins, n, ctypes.byref(wo), int(min_length), nw, buf, need.value,
+                                         ctypes.byref(need), un))
+    flat = list(buf[:need.value])
+    out, at = [], 0
+    for z, zm in enumerate(zmws):
+        nr = len(zm["reads"])
+        rows = []
+        for _ in range(nw[z]):
+            rows.append([None if flat[at + 4 * r] < 0 else tuple(flat[at + 4 * r:at + 4 * r + 4]) for r in range(nr)])
+            at += 4 * nr
+        out.append({"windows": window_plan(len(zm["draft"]), window, overlap), "slices": rows,
+                    "unanchored_reads": un[z]})
+    return out
+
+
+def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6, engine=None):
+    """Polish ZMWs with long drafts as overlapping windows (pbccs_polish_windowed).
+
+    Results as polish_zmws plus "windowed" (the draft had more than one window), "fallback" (0, or the reason code
+    the ZMW was polished whole for; WINDOW_FALLBACK names them), "unanchored_reads" and "windows": per window
+    begin, end, join (the draft position it is joined to the next window at, -1 for none), cut_begin / cut_end
+    (its piece of its own consensus), status, n_tested, n_applied."""
+    from . import default_engine
+    engine = engine or default_engine()
+    settings = settings or ConsensusSettings()
+    wo = window_options(window, overlap, guard, k)
+    m = _Marshalled(zmws)
+    n = len(zmws)
+    opts = settings._c()
+    info = (L.CWindowInfo * max(1, n))()
+    recs = []
+    for i, z in enumerate(zmws):
+        cap = len(window_plan(len(z["draft"]), window, overlap))
+        recs.append((L.CWindowRecord * cap)())
+        info[i].windows = recs[-1]
+        info[i].windows_cap = cap
+    L.check(L.load().pbccs_polish_windowed(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(wo), m._outs, info))
+    res = m.results()
+    for i, r in enumerate(res):
+        r["windowed"] = info[i].n_windows > 1
+        r["fallback"] = info[i].fallback
+        r["unanchored_reads"] = info[i].unanchored_reads
+        r["windows"] = [{"begin": w.begin, "end": w.end, "join": w.join, "cut_begin": w.cut_begin,
+                         "cut_end": w.cut_end, "status": w.status, "n_tested": w.n_tested, "n_applied": w.n_applied}
+                        for w in recs[i][:info[i].n_windows]]
+    return res
+
+
+def window_stats(engine=None, reset=False):
+    """The windowed polish's work since the last reset (pbccs_window_stats_get)."""
+    from . import default_engine
+    engine = engine or default_engine()
+    s = L.CWindowStats()
+    L.check(L.load().pbccs_window_stats_get(engine._h, ctypes.byref(s), 1 if reset else 0))
+    return {"zmws": s.zmws, "windows": s.windows, "fallbacks": list(s.fallbacks), "unanchored_reads": s.unanchored_reads,
+            "cut_tasks": s.cut_tasks, "joints": s.joints, "launches": s.launches, "slices_ms": s.slices_ms,
+            "polish_ms": s.polish_ms, "join_ms": s.join_ms, "fallback_ms": s.fallback_ms}
+
+
 def plan_batches(zmws, budget_bytes, max_per_batch=2000, max_len_ratio=1.5):
     """The work queue's batch plan (pbccs_plan_batches; host only, no device).
 
