@@ -611,7 +611,8 @@ int pbccs_poa_stats_get(pbccs_engine* eng, pbccs_poa_stats* out, int reset);
  * AlignAffineIupac (AffineAlignment.cpp:110-252: two-state affine, float32) for n independent pairs per call,
  * bit-exact: scores, ties and the traceback come out as the reference's.  The DP runs on the device
  * (k_align_fill, one move byte per cell and no score matrix in memory; k_align_trace).  AlignLinear is not
- * provided. */
+ * provided; long near-identical pairs have the certified band below (pbccs_align_batch_ex), which
+ * keeps these answers in memory linear in the band's width. */
 #define PBCCS_ALIGN_NW 0
 #define PBCCS_ALIGN_AFFINE 1
 #define PBCCS_ALIGN_AFFINE_IUPAC 2
@@ -663,6 +664,65 @@ typedef struct {
     long long groups;
 } pbccs_align_stats;
 int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset);
+
+/* ---- Certified banded fill for the pairwise aligners --------------------------------
+ * An opt-in for long, near-identical pairs; with band NULL or mode PBCCS_BAND_OFF every call is what it was.
+ * A band of half-width w holds the diagonals min(0, J - I) - w <= j - i <= max(0, J - I) + w.  The banded fill
+ * (k_align_fill_band) leaves move bytes only for its strips' column windows, about I (W + 64 R + 62) bytes for W
+ * band diagonals where the full fill leaves I J.  Its final score S bounds how far an optimal path can stray: every
+ * path that leaves the band scores at most U(w) (+ a rounding margin E for affine parameters that are not exact in
+ * float32), so when S > U(w) + E the banded score and transcript are the full fill's, bit for bit (a numerically
+ * zero affine score may differ in the sign of zero).  At most two banded fills per pair: the first at w (or the
+ * automatic width, 32), the second at the smallest width the first score certifies.  A pair that cannot be
+ * certified (Insert + Delete > max(Match, Mismatch); 2 max(GapOpen, GapExtend) > the largest diagonal score; sums
+ * out of the dead-cell value's range), whose band would cover the whole matrix or whose banded store would be no
+ * smaller than the full one, takes the full fill.  No banded answer is returned without its certificate. */
+#define PBCCS_BAND_OFF 0
+#define PBCCS_BAND_AUTO 1    /* first half-width chosen by the library */
+#define PBCCS_BAND_WIDTH 2   /* first half-width = w */
+typedef struct {
+    int mode;
+    int w;
+} pbccs_align_band;
+
+/* fallback reasons */
+#define PBCCS_BAND_CERTIFIED 0
+#define PBCCS_BAND_NOT_CERTIFIABLE 1
+#define PBCCS_BAND_COVERS_MATRIX 2
+#define PBCCS_BAND_STORE_NOT_SMALLER 3
+#define PBCCS_BAND_TRACE_FLAGGED 4
+#define PBCCS_BAND_UNCERTIFIED 5
+#define PBCCS_BAND_DEGENERATE 6   /* an empty sequence: answered on the host */
+#define PBCCS_BAND_OVER_BUDGET 7  /* the banded store alone exceeds the workspace; so does the full one (PBCCS_EOOM) */
+typedef struct {
+    int banded;     /* 1: a certified banded fill's answer; 0: the full fill's */
+    int w;          /* the last half-width tried */
+    int attempts;   /* banded fills of this pair: 0, 1 or 2 */
+    int reason;     /* PBCCS_BAND_*: why the pair took the full fill */
+} pbccs_align_band_info;
+
+/* pbccs_align_batch with the band.  info: NULL, or n entries. */
+int pbccs_align_batch_ex(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_pair* pairs, int n,
+                         pbccs_align_result* out, const pbccs_align_band* band, pbccs_align_band_info* info);
+
+/* U(w), E and whether the parameters can be certified at all, for a pair of query_len rows and target_len columns:
+ * host code, no engine.  *u is -infinity when no path can leave the band. */
+int pbccs_align_band_bound(const pbccs_align_params* params, int query_len, int target_len, int w, double* u,
+                           double* e, int* certifiable);
+/* The smallest half-width whose certificate a banded score (a lower bound of the full score) satisfies; -1 in *w
+ * when the pair cannot be certified.  Host code, no engine. */
+int pbccs_align_band_widen(const pbccs_align_params* params, int query_len, int target_len, double score, int* w);
+
+/* Banded work since the last reset: pairs given to banded calls, pairs answered banded, second attempts, fallbacks
+ * by reason (index PBCCS_BAND_*), cells inside the bands filled and I x J of the same pairs, banded move-store
+ * bytes, launches and groups, fill / trace device ms (profiling on). */
+typedef struct {
+    long long pairs, banded_pairs, second_attempts;
+    long long fallbacks[8];
+    long long band_cells, full_cells, launches, groups, trace_steps;
+    double store_bytes, fill_ms, trace_ms;
+} pbccs_align_band_stats;
+int pbccs_align_band_stats_get(pbccs_engine* eng, pbccs_align_band_stats* out, int reset);
 
 /* ---- MapToDraft: placing reads on a finished draft ---------------------------------------------------
  * What SparsePoa::OrientAndAddRead(read, minScoreToAdd) followed by FindConsensus reports for a read on a graph

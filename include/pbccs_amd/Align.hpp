@@ -11,6 +11,11 @@
 // PairwiseAlignment, FromTranscript and TargetToQueryPositions are host code; the aligners run on the device.
 // As in the reference, the aligners return a new PairwiseAlignment the caller deletes.  AlignBatch aligns many
 // pairs in one call.  AlignLinear is not provided.
+//
+// Not in the reference: every aligner takes a trailing BandOptions (default off).  BandOptions::Auto() or
+// BandOptions::Width(w) turns on the certified banded fill: a long, near-identical pair is filled
+// inside a band of diagonals, and the banded answer is returned only where its score proves it to be the full
+// fill's; every other pair takes the full fill.  The results are the same either way.
 #pragma once
 
 #include <algorithm>
@@ -55,6 +60,14 @@ inline AffineAlignmentParams IupacAwareAffineAlignmentParams()
 {
     return AffineAlignmentParams(0, -1.0f, -1.0f, -0.5f, -0.25f);
 }
+
+struct BandOptions {
+    int Mode;   // PBCCS_BAND_OFF / PBCCS_BAND_AUTO / PBCCS_BAND_WIDTH
+    int W;      // the first half-width (PBCCS_BAND_WIDTH)
+    static BandOptions Off() { return BandOptions{PBCCS_BAND_OFF, 0}; }
+    static BandOptions Auto() { return BandOptions{PBCCS_BAND_AUTO, 0}; }
+    static BandOptions Width(int w) { return BandOptions{PBCCS_BAND_WIDTH, w}; }
+};
 
 class PairwiseAlignment {
 public:
@@ -154,12 +167,15 @@ struct AlignOutput {
     std::vector<PairwiseAlignment*> alignments;   // caller deletes
     std::vector<int> intScores;                   // Align: Score(I, J)
     std::vector<float> floatScores;               // affine: max(M, GAP)(I, J)
+    std::vector<pbccs_align_band_info> bandInfo;  // with a band: what became of each pair
 };
 
 // (target, query) pairs through pbccs_align_batch.  The refusals the reference makes (and the ones it should)
 // are thrown before the engine is touched.
-inline AlignOutput RunAlign(pbccs_align_params p, const std::vector<std::pair<std::string, std::string>>& pairs)
+inline AlignOutput RunAlign(pbccs_align_params p, const std::vector<std::pair<std::string, std::string>>& pairs,
+                            BandOptions band = BandOptions::Off())
 {
+    if (band.Mode == PBCCS_BAND_WIDTH && band.W < 0) throw InvalidInputError("band half-width must be >= 0");
     if (p.kind == PBCCS_ALIGN_NW && p.mode != PBCCS_POA_GLOBAL)
         throw UnsupportedFeatureError("Only GLOBAL alignment supported at present");
     if (p.kind != PBCCS_ALIGN_NW &&
@@ -178,7 +194,13 @@ inline AlignOutput RunAlign(pbccs_align_params p, const std::vector<std::pair<st
     }
     AlignOutput r;
     if (n == 0) return r;
-    Check(pbccs_align_batch(DefaultEngine(), &p, in.data(), n, out.data()));
+    if (band.Mode == PBCCS_BAND_OFF) {
+        Check(pbccs_align_batch(DefaultEngine(), &p, in.data(), n, out.data()));
+    } else {
+        const pbccs_align_band b{band.Mode, band.W};
+        r.bandInfo.resize(n);
+        Check(pbccs_align_batch_ex(DefaultEngine(), &p, in.data(), n, out.data(), &b, r.bandInfo.data()));
+    }
     for (int k = 0; k < n; ++k) {
         PairwiseAlignment* a =
             PairwiseAlignment::FromTranscript(buf[k].substr(0, out[k].len), pairs[k].first, pairs[k].second);
@@ -209,53 +231,60 @@ inline pbccs_align_params AffineParams(int kind, const AffineAlignmentParams& a)
 }  // namespace detail
 
 inline PairwiseAlignment* Align(const std::string& target, const std::string& query, int* score,
-                                AlignConfig config = AlignConfig::Default())
+                                AlignConfig config = AlignConfig::Default(), BandOptions band = BandOptions::Off())
 {
-    detail::AlignOutput r = detail::RunAlign(detail::NwParams(config), {{target, query}});
+    detail::AlignOutput r = detail::RunAlign(detail::NwParams(config), {{target, query}}, band);
     if (score != NULL) *score = r.intScores[0];
     return r.alignments[0];
 }
 
 inline PairwiseAlignment* Align(const std::string& target, const std::string& query,
-                                AlignConfig config = AlignConfig::Default())
+                                AlignConfig config = AlignConfig::Default(), BandOptions band = BandOptions::Off())
 {
-    return Align(target, query, NULL, config);
+    return Align(target, query, NULL, config, band);
 }
 
 inline PairwiseAlignment* AlignAffine(const std::string& target, const std::string& query,
-                                      AffineAlignmentParams params = DefaultAffineAlignmentParams())
+                                      AffineAlignmentParams params = DefaultAffineAlignmentParams(),
+                                      BandOptions band = BandOptions::Off())
 {
-    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE, params), {{target, query}}).alignments[0];
+    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE, params), {{target, query}}, band).alignments[0];
 }
 
 inline PairwiseAlignment* AlignAffineIupac(const std::string& target, const std::string& query,
-                                           AffineAlignmentParams params = IupacAwareAffineAlignmentParams())
+                                           AffineAlignmentParams params = IupacAwareAffineAlignmentParams(),
+                                           BandOptions band = BandOptions::Off())
 {
-    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE_IUPAC, params), {{target, query}}).alignments[0];
+    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE_IUPAC, params), {{target, query}}, band)
+        .alignments[0];
 }
 
 // The vector forms: every (target, query) pair in one device call, results in input order; caller deletes.
-// scores (optional) receives Score(I, J) per pair.
+// scores (optional) receives Score(I, J) per pair; with a band, info (optional) receives what became of each pair.
 inline std::vector<PairwiseAlignment*> AlignBatch(const std::vector<std::pair<std::string, std::string>>& pairs,
                                                   AlignConfig config = AlignConfig::Default(),
-                                                  std::vector<int>* scores = NULL)
+                                                  std::vector<int>* scores = NULL,
+                                                  BandOptions band = BandOptions::Off(),
+                                                  std::vector<pbccs_align_band_info>* info = NULL)
 {
-    detail::AlignOutput r = detail::RunAlign(detail::NwParams(config), pairs);
+    detail::AlignOutput r = detail::RunAlign(detail::NwParams(config), pairs, band);
     if (scores) *scores = r.intScores;
+    if (info) *info = r.bandInfo;
     return r.alignments;
 }
 
 inline std::vector<PairwiseAlignment*> AlignAffineBatch(const std::vector<std::pair<std::string, std::string>>& pairs,
-                                                        AffineAlignmentParams params = DefaultAffineAlignmentParams())
+                                                        AffineAlignmentParams params = DefaultAffineAlignmentParams(),
+                                                        BandOptions band = BandOptions::Off())
 {
-    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE, params), pairs).alignments;
+    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE, params), pairs, band).alignments;
 }
 
 inline std::vector<PairwiseAlignment*> AlignAffineIupacBatch(
     const std::vector<std::pair<std::string, std::string>>& pairs,
-    AffineAlignmentParams params = IupacAwareAffineAlignmentParams())
+    AffineAlignmentParams params = IupacAwareAffineAlignmentParams(), BandOptions band = BandOptions::Off())
 {
-    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE_IUPAC, params), pairs).alignments;
+    return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE_IUPAC, params), pairs, band).alignments;
 }
 
 }  // namespace ConsensusCore

@@ -309,7 +309,7 @@ from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E4
 from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
 from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
-                    TargetToQueryPositions, UnsupportedFeatureError, align_batch, align_stats)
+                    TargetToQueryPositions, UnsupportedFeatureError, align_band_stats, align_batch, align_stats)
 from .mapping import map_batch, map_stats, map_to_draft  # noqa: E402,F401
 from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa: E402,F401
 

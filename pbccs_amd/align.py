@@ -4,7 +4,11 @@ AffineAlignment.hpp, AlignConfig.hpp) over the C ABI's pbccs_align_batch.
 Align (Needleman-Wunsch, int32), AlignAffine and AlignAffineIupac (two-state affine, float32) run in HIP
 (k_align_fill / k_align_trace), bit-exact with the reference: ties and the traceback come out the same.
 PairwiseAlignment, FromTranscript and TargetToQueryPositions are host-side value code.  There is no CPU
-fallback for the aligners: without the library or a GPU they raise.  AlignLinear is not provided."""
+fallback for the aligners: without the library or a GPU they raise.  AlignLinear is not provided.
+
+band= on align_batch and the three aligners turns on the certified banded fill: long,
+near-identical pairs are filled inside a band of diagonals and the answer is returned only when the banded score
+certifies that it is the full fill's; every other pair takes the full fill.  Off by default."""
 import ctypes
 import math
 
@@ -202,10 +206,49 @@ def _encode(s):
     return s if isinstance(s, bytes) else s.encode("latin-1")
 
 
-def align_batch_raw(pairs, kind, params=None, engine=None, caps=None):
+BAND_REASONS = ("certified", "not_certifiable", "covers_matrix", "store_not_smaller", "trace_flagged", "uncertified",
+                "degenerate", "over_budget")
+
+
+def _c_band(band):
+    """band=None / False: off; True: automatic first half-width; an int w >= 0: first half-width w."""
+    if band is None or band is False:
+        return None
+    b = _L.CAlignBand()
+    if band is True:
+        b.mode, b.w = 1, 0
+    else:
+        w = int(band)
+        if w < 0:
+            raise InvalidInputError("band half-width must be >= 0")
+        b.mode, b.w = 2, min(w, 2**31 - 1)
+    return b
+
+
+def align_band_bound(kind, query_len, target_len, w, params=None):
+    """(U(w), E, certifiable) of the band certificate for a pair of query_len rows and target_len columns: every
+    path that leaves the band of half-width w scores at most U + E.  Host code: no engine, no GPU."""
+    c = _c_params(kind, params)
+    u, e, ok = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _L.check(load().pbccs_align_band_bound(ctypes.byref(c), int(query_len), int(target_len), int(w), ctypes.byref(u),
+                                           ctypes.byref(e), ctypes.byref(ok)))
+    return u.value, e.value, bool(ok.value)
+
+
+def align_band_widen(kind, query_len, target_len, score, params=None):
+    """The smallest half-width that a banded score certifies, or -1.  Host code: no engine, no GPU."""
+    c = _c_params(kind, params)
+    w = ctypes.c_int()
+    _L.check(load().pbccs_align_band_widen(ctypes.byref(c), int(query_len), int(target_len), float(score),
+                                           ctypes.byref(w)))
+    return w.value
+
+
+def align_batch_raw(pairs, kind, params=None, engine=None, caps=None, band=None, info=None):
     """pbccs_align_batch as it stands: (return code, [(transcript, score, status, len) per pair]).  pairs are
     (target, query) strings; caps overrides the transcript capacities (default target + query lengths).
-    Marshalling is flat: one blob with pointer tables and one shared transcript buffer."""
+    Marshalling is flat: one blob with pointer tables and one shared transcript buffer.  band: see _c_band; info:
+    a list that receives one {"banded", "w", "attempts", "reason"} per pair of a banded call."""
     import numpy as np
     from .quiver import _struct_dtype
     c = _c_params(kind, params)
@@ -232,8 +275,20 @@ def align_batch_raw(pairs, kind, params=None, engine=None, caps=None):
         ins["query_len"][:n] = lens[1::2]
         outs["transcript"][:n] = ctypes.addressof(obuf) + ostart[:-1]
         outs["cap"][:n] = cap
-    rc = load().pbccs_align_batch(engine._h, ctypes.byref(c), ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CAlignPair)),
-                                  n, ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CAlignResult)))
+    cb = _c_band(band)
+    if cb is None:
+        rc = load().pbccs_align_batch(engine._h, ctypes.byref(c),
+                                      ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CAlignPair)), n,
+                                      ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CAlignResult)))
+    else:
+        binfo = (_L.CAlignBandInfo * max(1, n))()
+        rc = load().pbccs_align_batch_ex(engine._h, ctypes.byref(c),
+                                         ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CAlignPair)), n,
+                                         ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CAlignResult)),
+                                         ctypes.byref(cb), binfo)
+        if info is not None:
+            info[:] = [{"banded": bool(binfo[k].banded), "w": binfo[k].w, "attempts": binfo[k].attempts,
+                        "reason": BAND_REASONS[binfo[k].reason]} for k in range(n)]
     raw = obuf.raw
     os_, ln, caps_l, st = ostart.tolist(), outs["len"][:n].tolist(), cap.tolist(), outs["status"][:n].tolist()
     score = outs["score_i"][:n].tolist() if kind == NW else outs["score_f"][:n].tolist()
@@ -266,11 +321,14 @@ def _from_device_transcript(tr, target, query):
     return a
 
 
-def align_batch(pairs, kind, params=None, engine=None):
+def align_batch(pairs, kind, params=None, engine=None, band=None, return_info=False):
     """Aligns many (target, query) pairs in one call.  kind: NW (params: AlignConfig), AFFINE or AFFINE_IUPAC
     (params: AffineAlignmentParams).  Returns ([PairwiseAlignment], [score]) in input order; the score is
-    Score(I, J) (int) for NW and max(M, GAP)(I, J) (float32 value) for the affine kinds."""
-    rc, res = align_batch_raw(pairs, kind, params, engine)
+    Score(I, J) (int) for NW and max(M, GAP)(I, J) (float32 value) for the affine kinds.  band=True (automatic
+    first half-width) or band=w turns on the certified banded fill, whose answers are the full fill's;
+    return_info=True appends the per-pair records (banded, w, attempts, reason) as a third value."""
+    info = []
+    rc, res = align_batch_raw(pairs, kind, params, engine, band=band, info=info)
     _L.check(rc)
     alns = []
     for (t, q), (tr, _, _, _) in zip(pairs, res):
@@ -278,23 +336,27 @@ def align_batch(pairs, kind, params=None, engine=None):
         if a is None:
             raise _L.PbccsError(-3, "the device returned a transcript that does not map the target onto the query")
         alns.append(a)
+    if return_info:
+        if not info:
+            info = [{"banded": False, "w": 0, "attempts": 0, "reason": "certified"} for _ in pairs]
+        return alns, [r[1] for r in res], info
     return alns, [r[1] for r in res]
 
 
-def Align(target, query, config=None, return_score=False, engine=None):
+def Align(target, query, config=None, return_score=False, engine=None, band=None):
     """PairwiseAlignment* Align(target, query, int* score, AlignConfig) (PairwiseAlignment.cpp:125-212)."""
-    alns, scores = align_batch([(target, query)], NW, config, engine)
+    alns, scores = align_batch([(target, query)], NW, config, engine, band=band)
     return (alns[0], scores[0]) if return_score else alns[0]
 
 
-def AlignAffine(target, query, params=None, engine=None):
+def AlignAffine(target, query, params=None, engine=None, band=None):
     """AlignAffine(target, query, AffineAlignmentParams = DefaultAffineAlignmentParams())."""
-    return align_batch([(target, query)], AFFINE, params, engine)[0][0]
+    return align_batch([(target, query)], AFFINE, params, engine, band=band)[0][0]
 
 
-def AlignAffineIupac(target, query, params=None, engine=None):
+def AlignAffineIupac(target, query, params=None, engine=None, band=None):
     """AlignAffineIupac(target, query, AffineAlignmentParams = IupacAwareAffineAlignmentParams())."""
-    return align_batch([(target, query)], AFFINE_IUPAC, params, engine)[0][0]
+    return align_batch([(target, query)], AFFINE_IUPAC, params, engine, band=band)[0][0]
 
 
 def align_stats(engine=None, reset=False):
@@ -304,3 +366,15 @@ def align_stats(engine=None, reset=False):
     s = _L.CAlignStats()
     _L.check(load().pbccs_align_stats_get(engine._h, ctypes.byref(s), 1 if reset else 0))
     return {k: getattr(s, k) for k, _ in _L.CAlignStats._fields_}
+
+
+def align_band_stats(engine=None, reset=False):
+    """Banded-fill work since the last reset; fallbacks is a dict by reason."""
+    if engine is None:
+        from . import default_engine
+        engine = default_engine()
+    s = _L.CAlignBandStats()
+    _L.check(load().pbccs_align_band_stats_get(engine._h, ctypes.byref(s), 1 if reset else 0))
+    d = {k: getattr(s, k) for k, _ in _L.CAlignBandStats._fields_ if k != "fallbacks"}
+    d["fallbacks"] = {BAND_REASONS[k]: s.fallbacks[k] for k in range(1, len(BAND_REASONS))}
+    return d

@@ -8,7 +8,8 @@
 // through a small per-pair buffer.  No score matrix reaches HBM: each cell leaves one move byte (the traceback's
 // decision, taken from the very values the fill computed), stored by (strip, step, lane, row-in-lane) so that a
 // step's store is one contiguous 64 R-byte write.  k_align_trace walks the bytes, one thread per pair.
-// DESIGN.md §3.14.
+// DESIGN.md §3.14.  RunBanded is the opt-in certified band for long near-identical pairs (align_band.hpp,
+// align_band_kernels.hip); Run and RunKeep do not use it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +26,7 @@ namespace align {
 constexpr int kNw = 0, kAffine = 1, kAffineIupac = 2;   // PBCCS_ALIGN_*
 constexpr int kRowsPerLane[3] = {2, 4, 8};              // the compiled R values: strips of 128, 256, 512 rows
 constexpr int kTraceFlagged = 1;                        // trace status: the walk in M reached row 0 or column 0
+constexpr int kTraceLeftBand = 2;                       // banded trace status: the walk would read outside the band
 
 struct AlignScoring {
     int kind;
@@ -54,6 +56,39 @@ struct AlignStats {
     long long pairs = 0, cells = 0, launches = 0, traceSteps = 0, groups = 0;
     double fillMs = 0.0, traceMs = 0.0;
     double bytes = 0.0;   // move-store bytes the fills covered
+};
+
+// One pair of a banded fill (align_band.hpp): the band's diagonals lo <= j - i <= hi and the
+// steps T of one strip in the store, nStrips x T x 64 lanes x R rows.
+struct AlignBandJob {
+    long long storeOff, seqOff, carryOff, outOff;   // as AlignJob's
+    int I, J;
+    int R, nStrips;
+    int lo, hi;
+    int T, pad;
+};
+
+// The banded route is off unless asked for.  w < 0: the automatic first half-width.
+struct BandOptions {
+    bool on = false;
+    long long w = -1;
+};
+
+// What became of one pair of a banded call.
+struct BandInfo {
+    int banded = 0;     // 1: the answer is a certified banded fill's; 0: the full fill's (or the host's)
+    int w = 0;          // the last half-width tried
+    int attempts = 0;   // banded fills of this pair: 0, 1 or 2
+    int reason = 0;     // why the pair took the full fill (kBand*), 0 for a banded pair
+};
+
+struct AlignBandStats {
+    long long pairs = 0, bandedPairs = 0, secondAttempts = 0;
+    long long fallbacks[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // by reason
+    long long bandCells = 0, fullCells = 0;              // cells inside the bands filled; I x J of the same pairs
+    long long launches = 0, groups = 0, traceSteps = 0;
+    double storeBytes = 0.0;                             // banded move-store bytes the fills covered
+    double fillMs = 0.0, traceMs = 0.0;
 };
 
 struct PairView {
@@ -96,17 +131,28 @@ public:
     void RunKeep(const AlignScoring& p, const PairView* pairs, int n, std::vector<KeptTranscript>* out);
     const uint8_t* TranscriptsDevice() const { return dOut_.ptr; }
 
+    // Run with the certified band (align_band.hpp): at most two banded fills per pair, the second at the width the
+    // first one's score calls for; a pair's banded answer is returned only when its certificate holds, every other
+    // pair goes through Run.  info (optional, n entries) says what became of each pair.
+    void RunBanded(const AlignScoring& p, const PairView* pairs, int n, PairResult* out, const BandOptions& band,
+                   BandInfo* info);
+
     AlignStats stats;
+    AlignBandStats bandStats;
     bool profiling = false;
 
 private:
     void RunImpl(const AlignScoring& p, const PairView* pairs, int n, PairResult* out,
                  std::vector<KeptTranscript>* keep);
+    void BandAttempt(const AlignScoring& p, const PairView* pairs, const std::vector<int>& idx,
+                     const std::vector<long long>& ws, PairResult* out, std::vector<double>* scoreOut,
+                     std::vector<int>* verdict);
     int device_;
     hipStream_t stream_ = nullptr;
     hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
     DevVec<uint8_t> dSeq_, dStore_, dOut_;
     DevVec<AlignJob> dJobs_;
+    DevVec<AlignBandJob> dBandJobs_;
     DevVec<int> dList_, dLens_, dStatus_;
     DevVec<uint32_t> dCarry_, dScores_;
 };

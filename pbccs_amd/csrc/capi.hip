@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "align_band.hpp"
 #include "align_kernels.hpp"
 #include "engine.hpp"
 #include "driver.hpp"
@@ -2268,6 +2269,12 @@ int pbccs_poa_stats_get(pbccs_engine* eng, pbccs_poa_stats* out, int reset)
 int pbccs_align_batch(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_pair* pairs, int n,
                       pbccs_align_result* out)
 {
+    return pbccs_align_batch_ex(eng, params, pairs, n, out, nullptr, nullptr);
+}
+
+int pbccs_align_batch_ex(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_pair* pairs, int n,
+                         pbccs_align_result* out, const pbccs_align_band* band, pbccs_align_band_info* info)
+{
     if (!eng || !params || n < 0 || (n > 0 && (!pairs || !out))) return fail(PBCCS_EINVAL, "bad argument");
     const pbccs_align_params& a = *params;
     if (a.kind != PBCCS_ALIGN_NW && a.kind != PBCCS_ALIGN_AFFINE && a.kind != PBCCS_ALIGN_AFFINE_IUPAC)
@@ -2278,6 +2285,9 @@ int pbccs_align_batch(pbccs_engine* eng, const pbccs_align_params* params, const
         !(std::isfinite(a.match_score) && std::isfinite(a.mismatch_score) && std::isfinite(a.gap_open) &&
           std::isfinite(a.gap_extend) && std::isfinite(a.partial_match_score)))
         return fail(PBCCS_EINVAL, "affine alignment parameters must be finite");
+    if (band && band->mode != PBCCS_BAND_OFF && band->mode != PBCCS_BAND_AUTO && band->mode != PBCCS_BAND_WIDTH)
+        return fail(PBCCS_EINVAL, "unknown band mode");
+    if (band && band->mode == PBCCS_BAND_WIDTH && band->w < 0) return fail(PBCCS_EINVAL, "negative band half-width");
     for (int k = 0; k < n; ++k) {
         const pbccs_align_pair& p = pairs[k];
         if (p.target_len < 0 || p.query_len < 0 || (p.target_len > 0 && !p.target) || (p.query_len > 0 && !p.query))
@@ -2292,7 +2302,20 @@ int pbccs_align_batch(pbccs_engine* eng, const pbccs_align_params* params, const
         std::vector<align::PairResult> res(n);
         {
             std::lock_guard<std::mutex> lk(eng->alignMu);
-            eng->Align().Run(sc, pv.data(), n, res.data());
+            if (band && band->mode != PBCCS_BAND_OFF) {
+                align::BandOptions bo;
+                bo.on = true;
+                bo.w = band->mode == PBCCS_BAND_WIDTH ? band->w : -1;
+                std::vector<align::BandInfo> bi((size_t)n);
+                eng->Align().RunBanded(sc, pv.data(), n, res.data(), bo, bi.data());
+                if (info)
+                    for (int k = 0; k < n; ++k)
+                        info[k] = pbccs_align_band_info{bi[k].banded, bi[k].w, bi[k].attempts, bi[k].reason};
+            } else {
+                eng->Align().Run(sc, pv.data(), n, res.data());
+                if (info)
+                    for (int k = 0; k < n; ++k) info[k] = pbccs_align_band_info{0, 0, 0, 0};
+            }
         }
         int rc = PBCCS_OK;
         bool small = false;
@@ -2330,6 +2353,63 @@ int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset)
         const align::AlignStats s = eng->align ? eng->align->stats : align::AlignStats();
         *out = pbccs_align_stats{s.pairs, s.cells, s.launches, s.traceSteps, s.fillMs, s.traceMs, s.bytes, s.groups};
         if (reset && eng->align) eng->align->stats = align::AlignStats();
+        return PBCCS_OK;
+    });
+}
+
+namespace {
+align::AlignScoring band_scoring(const pbccs_align_params& a)
+{
+    return align::AlignScoring{a.kind,        a.match,          a.mismatch, a.insert,     a.delete_,
+                               a.match_score, a.mismatch_score, a.gap_open, a.gap_extend, a.partial_match_score};
+}
+bool band_args_ok(const pbccs_align_params* a, int I, int J)
+{
+    return a && I >= 0 && J >= 0 &&
+           (a->kind == PBCCS_ALIGN_NW || a->kind == PBCCS_ALIGN_AFFINE || a->kind == PBCCS_ALIGN_AFFINE_IUPAC);
+}
+}  // namespace
+
+int pbccs_align_band_bound(const pbccs_align_params* params, int query_len, int target_len, int w, double* u,
+                           double* e, int* certifiable)
+{
+    if (!band_args_ok(params, query_len, target_len) || w < 0 || !u || !e || !certifiable)
+        return fail(PBCCS_EINVAL, "bad argument");
+    const align::BandBound b = align::band_bound(band_scoring(*params), query_len, target_len, w);
+    *u = b.U;
+    *e = b.E;
+    *certifiable = b.certifiable ? 1 : 0;
+    return PBCCS_OK;
+}
+
+int pbccs_align_band_widen(const pbccs_align_params* params, int query_len, int target_len, double score, int* w)
+{
+    if (!band_args_ok(params, query_len, target_len) || !w) return fail(PBCCS_EINVAL, "bad argument");
+    *w = (int)align::band_widen(band_scoring(*params), query_len, target_len, score);
+    return PBCCS_OK;
+}
+
+int pbccs_align_band_stats_get(pbccs_engine* eng, pbccs_align_band_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->alignMu);
+        const align::AlignBandStats s = eng->align ? eng->align->bandStats : align::AlignBandStats();
+        pbccs_align_band_stats o{};
+        o.pairs = s.pairs;
+        o.banded_pairs = s.bandedPairs;
+        o.second_attempts = s.secondAttempts;
+        for (int k = 0; k < 8; ++k) o.fallbacks[k] = s.fallbacks[k];
+        o.band_cells = s.bandCells;
+        o.full_cells = s.fullCells;
+        o.launches = s.launches;
+        o.groups = s.groups;
+        o.trace_steps = s.traceSteps;
+        o.store_bytes = s.storeBytes;
+        o.fill_ms = s.fillMs;
+        o.trace_ms = s.traceMs;
+        *out = o;
+        if (reset && eng->align) eng->align->bandStats = align::AlignBandStats();
         return PBCCS_OK;
     });
 }

@@ -183,6 +183,22 @@ class CAlignStats(ctypes.Structure):
                 ("bytes", ctypes.c_double), ("groups", ctypes.c_longlong)]
 
 
+class CAlignBand(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("w", ctypes.c_int)]
+
+
+class CAlignBandInfo(ctypes.Structure):
+    _fields_ = [("banded", ctypes.c_int), ("w", ctypes.c_int), ("attempts", ctypes.c_int), ("reason", ctypes.c_int)]
+
+
+class CAlignBandStats(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_longlong), ("banded_pairs", ctypes.c_longlong),
+                ("second_attempts", ctypes.c_longlong), ("fallbacks", ctypes.c_longlong * 8),
+                ("band_cells", ctypes.c_longlong), ("full_cells", ctypes.c_longlong),
+                ("launches", ctypes.c_longlong), ("groups", ctypes.c_longlong), ("trace_steps", ctypes.c_longlong),
+                ("store_bytes", ctypes.c_double), ("fill_ms", ctypes.c_double), ("trace_ms", ctypes.c_double)]
+
+
 class CMapInput(ctypes.Structure):
     _fields_ = [("draft", ctypes.c_char_p), ("draft_len", ctypes.c_int), ("seqs", ctypes.POINTER(ctypes.c_char_p)),
                 ("lens", ctypes.POINTER(ctypes.c_int)), ("n_reads", ctypes.c_int)]
@@ -358,6 +374,14 @@ SIGNATURES = {
     "pbccs_align_batch": (I, [P, ctypes.POINTER(CAlignParams), ctypes.POINTER(CAlignPair), I,
                               ctypes.POINTER(CAlignResult)]),
     "pbccs_align_stats_get": (I, [P, ctypes.POINTER(CAlignStats), I]),
+    # the certified band
+    "pbccs_align_batch_ex": (I, [P, ctypes.POINTER(CAlignParams), ctypes.POINTER(CAlignPair), I,
+                                 ctypes.POINTER(CAlignResult), ctypes.POINTER(CAlignBand),
+                                 ctypes.POINTER(CAlignBandInfo)]),
+    "pbccs_align_band_bound": (I, [ctypes.POINTER(CAlignParams), I, I, I, ctypes.POINTER(ctypes.c_double),
+                                   ctypes.POINTER(ctypes.c_double), PI]),
+    "pbccs_align_band_widen": (I, [ctypes.POINTER(CAlignParams), I, I, ctypes.c_double, PI]),
+    "pbccs_align_band_stats_get": (I, [P, ctypes.POINTER(CAlignBandStats), I]),
     "pbccs_ccs_batch": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.c_longlong, ctypes.POINTER(CPolishOptions),
                             ctypes.POINTER(CCcsOutput)]),
     # MapToDraft and the capped ccs that keeps every pass
