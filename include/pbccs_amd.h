@@ -237,6 +237,8 @@ typedef struct {
     long long uncertain_reads;   /* ... reads re-run exactly (a fill decision or the AddRead gate within the bound) */
     long long exact_rounds;      /* ... ZMW rounds re-scored on exact bands (a score decision within the bound) */
     long long uncertain_why[4];  /* ... uncertain fills by decision: band end, begin hint, loop entry, final mismatch */
+    long long repeat_skipped_ckpt; /* pbccs_polish_batch_ex: ZMWs whose repeat round was skipped because a read keeps
+                                    checkpointed bands */
 } pbccs_counters;
 int pbccs_engine_counters(pbccs_engine* eng, pbccs_counters* out, int reset);
 
@@ -333,8 +335,10 @@ int pbccs_quiver_consensus_qvs(pbccs_quiver_scorer* s, int* qvs, int cap, int* n
  * deletion start < end and n_bases == 0, a substitution n_bases == end - start (Mutation-inl.hpp:102-115).
  * Bases are A, C, G, T and the reference's phony test bases M and N, complements of each other
  * (Sequence.cpp:41-78).  n_bases <= 7: the reference's extend buffer has 8 columns (EXTEND_BUFFER_COLUMNS,
- * asserted at Quiver/MutationScorer.cpp:177).  The Arrow scorer takes single-base mutations only, as the
- * reference's does (Arrow/MutationScorer.cpp:181-183). */
+ * asserted at Quiver/MutationScorer.cpp:177).  The Arrow scorer takes them too, through its own _ex calls
+ * below ("Arrow: mutations of any width"): A, C, G and T only there.  The reference's Arrow scorer refuses
+ * |LengthDiff| > 1 (Arrow/MutationScorer.cpp:181-183); pbccs_mutation and the calls that take it stay
+ * single-base. */
 typedef struct {
     int type;
     int start;
@@ -461,6 +465,48 @@ int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* c
                                  int n_configs, const pbccs_quiver_zmw* zmws, int n, const pbccs_refine_options* opts,
                                  const pbccs_repeat_options* repeats, long long* repeat_tested,
                                  long long* repeat_applied, pbccs_quiver_result* out);
+
+/* ---- Arrow: mutations of any width -------------------------------------------------
+ * The twins of pbccs_scorer_score_many / _scores / _is_favorable / _apply_mutations for pbccs_mutation_ex, and
+ * RefineRepeats for the Arrow scorer.  The reference's Arrow MutationScorer::ScoreMutation is written for any
+ * length behind a guard that refuses |LengthDiff| > 1, and its template pair holds a two-slot virtual mutation;
+ * these calls run ScoreMutation's four cases over a template view that holds the whole mutation (k_score_wide);
+ * a mutation three or more bases wide takes the last of them, the refill of the window (k_score_wide_refill),
+ * because the bands of the unmutated template do not hold its paths.
+ * They always take that kernel, at width 1 too, where the scores equal the single-base calls' bit for bit.
+ * The 8-column rule: the extension columns every active scoring read needs -- 1 + n_bases in the middle of its
+ * window (2 for a deletion), up to the window's end or start in the edge cases -- are derived on the host from
+ * the oriented, clipped mutation; more than 8 on any read, n_bases > 7, a base outside A, C, G, T or a mutation
+ * outside the template is PBCCS_EINVAL before anything is launched.  A scorer with a read on checkpointed bands
+ *  is PBCCS_EINVAL too: k_score_wide reads stored columns only.  The scorer stays usable. */
+int pbccs_scorer_score_many_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int n, double fast_threshold,
+                               double* scores);
+/* per_read holds NumReads() entries; `unscored` where a read is inactive or does not score the mutation */
+int pbccs_scorer_scores_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, double unscored, double* per_read);
+int pbccs_scorer_is_favorable_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int fast, int* favorable);
+/* ApplyMutations with the reads' windows remapped by TargetToQueryPositions, then the refill.  Overlapping
+ * edits, edits outside the template and an insertion at the template's end are PBCCS_EINVAL. */
+int pbccs_scorer_apply_mutations_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int n);
+/* RefineRepeats for the Arrow scorer: AbstractRefineConsensus (Consensus-inl.hpp:159-251) over
+ * RepeatMutationEnumerator, the favourable test Score(m, FastScoreThreshold) > 0.04.  opts NULL = {2, 3, 1, 10, 20}
+ * (see pbccs_quiver_refine_repeats).  n_tested / n_applied are set, not added to. */
+int pbccs_refine_repeats(pbccs_scorer* s, const pbccs_repeat_options* opts, long long* n_tested,
+                         long long* n_applied, int* converged);
+/* Host-only: the extension columns one read with window [tstart, tend) on `strand` needs for the mutation.
+ * *columns = -1: the read does not score it; 0: the whole-window refill (no extension buffer); -2: the mutated
+ * window would be empty.  -2 and *columns > 8 are what the calls above refuse. */
+int pbccs_wide_columns_needed(const pbccs_mutation_ex* m, int strand, int tstart, int tend, int* columns);
+/* pbccs_polish_batch with RefineRepeats between RefineConsensus and ConsensusQVs for every ZMW RefineConsensus
+ * converged on, the repeat rounds batched across the ZMWs of a device batch (one k_score_wide launch and one
+ * refill per round).  Records equal the per-scorer sequence RefineConsensus, RefineRepeats, ConsensusQVs.
+ * repeat_tested / repeat_applied (n entries each, may be NULL) receive RefineRepeats' counts (0 where it did not
+ * run).  A ZMW with a read on checkpointed bands skips the repeat round and finishes as pbccs_polish_batch does
+ * (pbccs_counters.repeat_skipped_ckpt counts it); a ZMW whose repeat round is refused (the 8-column rule, an
+ * edit that cannot be applied) ends PBCCS_ZMW_OTHER.  With repeats the batch fills exactly (no certified fast
+ * path, no band reclaim).  repeats == NULL is exactly pbccs_polish_batch. */
+int pbccs_polish_batch_ex(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                          const pbccs_repeat_options* repeats, long long* repeat_tested, long long* repeat_applied,
+                          pbccs_zmw_output* out);
 
 /* ---- Diploid site calling (ConsensusCore Arrow/Diploid.cpp:94-241, Quiver/Diploid.cpp) -----------------
  * A site's scores are n_reads x 9 floats, rows in AddRead order (inactive reads included), columns

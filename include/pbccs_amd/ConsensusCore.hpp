@@ -113,7 +113,7 @@ public:
     {
         return newBases_.size() <= 1 && end_ - start_ == (type_ == INSERTION ? 0 : 1);
     }
-    // any width (Quiver's _ex entry points); new_bases points into this Mutation
+    // any width (the _ex entry points of either scorer family); new_bases points into this Mutation
     pbccs_mutation_ex ToCEx() const
     {
         pbccs_mutation_ex m;
@@ -303,10 +303,17 @@ public:
     }
     AddReadResult AddRead(const MappedArrowRead& mr) { return AddRead(mr, config_.AddThreshold); }
 
+    // A mutation wider than one base goes to the pbccs_scorer_*_ex calls (k_score_wide); the
+    // reference's scorer throws for it (Arrow/MutationScorer.cpp:181-183).  Single-base ones stay where they were.
     double Score(const Mutation& m, double fastScoreThreshold = -DBL_MAX)
     {
-        const pbccs_mutation c = m.ToC();
         double v = 0.0;
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_scorer_score_many_ex(handle_, &x, 1, fastScoreThreshold, &v));
+            return v;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_scorer_score(handle_, &c, fastScoreThreshold, &v));
         return v;
     }
@@ -314,8 +321,13 @@ public:
     double FastScore(const Mutation& m) { return Score(m, config_.FastScoreThreshold); }
     std::vector<double> Scores(const Mutation& m, double unscoredValue = 0.0)
     {
-        const pbccs_mutation c = m.ToC();
         std::vector<double> out(NumReads());
+        if (!m.IsSingleBase()) {
+            const pbccs_mutation_ex x = m.ToCEx();
+            detail::Check(pbccs_scorer_scores_ex(handle_, &x, unscoredValue, out.data()));
+            return out;
+        }
+        const pbccs_mutation c = m.ToC();
         detail::Check(pbccs_scorer_scores(handle_, &c, unscoredValue, out.data()));
         return out;
     }
@@ -323,6 +335,14 @@ public:
     bool FastIsFavorable(const Mutation& m) { return FastScore(m) > 0.04; }
     void ApplyMutations(const std::vector<Mutation>& muts)
     {
+        bool wide = false;
+        for (const Mutation& m : muts) wide = wide || !m.IsSingleBase();
+        if (wide) {
+            std::vector<pbccs_mutation_ex> x;
+            for (const Mutation& m : muts) x.push_back(m.ToCEx());
+            detail::Check(pbccs_scorer_apply_mutations_ex(handle_, x.data(), (int)x.size()));
+            return;
+        }
         std::vector<pbccs_mutation> c;
         for (const Mutation& m : muts) c.push_back(m.ToC());
         detail::Check(pbccs_scorer_apply_mutations(handle_, c.data(), (int)c.size()));
@@ -399,6 +419,31 @@ inline bool RefineConsensus(Arrow::ArrowMultiReadMutationScorer& mms, size_t* nT
     *nTested += (size_t)nt;
     *nApplied += (size_t)na;
     return conv != 0;
+}
+
+// RefineRepeats / RefineDinucleotideRepeats (Consensus.hpp:69-76) for the Arrow scorer (pbccs_refine_repeats).
+// RefineRepeatOptions sets MaximumIterations = 1 and leaves the other two fields unset; DefaultRefineOptions' 10
+// and 20 stand in, as for the Quiver scorers (Quiver.hpp).
+inline bool RefineRepeats(Arrow::ArrowMultiReadMutationScorer& mms, int repeatLength, int minRepeatElements = 3,
+                          size_t* nTested = nullptr, size_t* nApplied = nullptr, int maximumIterations = 1)
+{
+    pbccs_repeat_options o;
+    o.repeat_length = repeatLength;
+    o.min_repeat_elements = minRepeatElements;
+    o.max_iterations = maximumIterations;
+    o.mutation_separation = DefaultRefineOptions.MutationSeparation;
+    o.mutation_neighborhood = DefaultRefineOptions.MutationNeighborhood;
+    long long nt = 0, na = 0;
+    int conv = 0;
+    detail::Check(pbccs_refine_repeats(mms.Handle(), &o, &nt, &na, &conv));
+    if (nTested) *nTested += (size_t)nt;
+    if (nApplied) *nApplied += (size_t)na;
+    return conv != 0;
+}
+
+inline bool RefineDinucleotideRepeats(Arrow::ArrowMultiReadMutationScorer& mms, int minDinucleotideRepeatElements = 3)
+{
+    return RefineRepeats(mms, 2, minDinucleotideRepeatElements);
 }
 
 inline std::vector<int> ConsensusQVs(Arrow::ArrowMultiReadMutationScorer& mms)

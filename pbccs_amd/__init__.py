@@ -31,8 +31,9 @@ class Mutation:
     """ConsensusCore::Mutation (Mutation.hpp:56-129).  Mutation(type, position, base) is the single-base form;
     a multi-character `base` string or an `end` gives a mutation of any width (Mutation-inl.hpp:53-77): an
     insertion of the string at `position`, a substitution of [position, position + len(base)), a deletion of
-    [position, end).  Multi-base mutations are a Quiver feature: the Arrow scorer refuses them, as the
-    reference's does (Arrow/MutationScorer.cpp:181-183)."""
+    [position, end).  The Quiver scorer takes them as they come; the Arrow scorer takes them where the call says
+    wide=True (k_score_wide) and refuses them otherwise, as the reference's does
+    (Arrow/MutationScorer.cpp:181-183)."""
 
     __slots__ = ("type", "start", "end", "new_base")
 
@@ -58,7 +59,8 @@ class Mutation:
 
     def _c(self):
         if not self.is_single_base():
-            raise _lib_mod.PbccsError(-1, "multi-base mutations are scored by the Quiver scorer only")
+            raise _lib_mod.PbccsError(-1, "multi-base mutation: the Arrow scorer takes it with wide=True, the Quiver "
+                                          "scorer as it is")
         return _lib_mod.CMutation(self.type, self.start, self.end, self.new_base.encode()[:1] or b"-")
 
     def _cx(self):
@@ -185,36 +187,60 @@ class ArrowMultiReadMutationScorer:
                                                     float(threshold), ctypes.byref(res)))
         return res.value
 
-    def Score(self, m, fast_score_threshold=-DBL_MAX):
+    # wide=True: the pbccs_scorer_*_ex calls (k_score_wide), which take mutations of any width --
+    # Mutation(type, pos, "AC") -- and single-base ones too, scored bit for bit as the default path scores them.
+    # Without it a multi-base mutation is refused, as before.
+    def Score(self, m, fast_score_threshold=-DBL_MAX, wide=False):
+        if wide:
+            return self.ScoreMany([m], fast_score_threshold, wide=True)[0]
         v = ctypes.c_double()
         _lib_mod.check(load().pbccs_scorer_score(self._h, ctypes.byref(m._c()), fast_score_threshold, ctypes.byref(v)))
         return v.value
 
-    def FastScore(self, m):
-        return self.Score(m, self.config.fast_score_threshold)
+    def FastScore(self, m, wide=False):
+        return self.Score(m, self.config.fast_score_threshold, wide=wide)
 
-    def ScoreMany(self, muts, fast_score_threshold=-DBL_MAX):
-        arr = (_lib_mod.CMutation * max(1, len(muts)))(*[m._c() for m in muts])
+    def ScoreMany(self, muts, fast_score_threshold=-DBL_MAX, wide=False):
         out = (ctypes.c_double * max(1, len(muts)))()
+        if wide:
+            cs = [m._cx() for m in muts]   # (the list keeps the base strings alive through the call)
+            arr = (_lib_mod.CMutationEx * max(1, len(muts)))(*cs)
+            _lib_mod.check(load().pbccs_scorer_score_many_ex(self._h, arr, len(muts), fast_score_threshold, out))
+            return list(out[: len(muts)])
+        arr = (_lib_mod.CMutation * max(1, len(muts)))(*[m._c() for m in muts])
         _lib_mod.check(load().pbccs_scorer_score_many(self._h, arr, len(muts), fast_score_threshold, out))
         return list(out[: len(muts)])
 
-    def Scores(self, m, unscored_value=0.0):
+    def Scores(self, m, unscored_value=0.0, wide=False):
         out = (ctypes.c_double * max(1, self.NumReads()))()
-        _lib_mod.check(load().pbccs_scorer_scores(self._h, ctypes.byref(m._c()), unscored_value, out))
+        if wide:
+            c = m._cx()
+            _lib_mod.check(load().pbccs_scorer_scores_ex(self._h, ctypes.byref(c), unscored_value, out))
+        else:
+            _lib_mod.check(load().pbccs_scorer_scores(self._h, ctypes.byref(m._c()), unscored_value, out))
         return list(out[: self.NumReads()])
 
-    def IsFavorable(self, m):
+    def _favorable(self, m, fast, wide):
         f = ctypes.c_int()
-        _lib_mod.check(load().pbccs_scorer_is_favorable(self._h, ctypes.byref(m._c()), 0, ctypes.byref(f)))
+        if wide:
+            c = m._cx()
+            _lib_mod.check(load().pbccs_scorer_is_favorable_ex(self._h, ctypes.byref(c), fast, ctypes.byref(f)))
+        else:
+            _lib_mod.check(load().pbccs_scorer_is_favorable(self._h, ctypes.byref(m._c()), fast, ctypes.byref(f)))
         return bool(f.value)
 
-    def FastIsFavorable(self, m):
-        f = ctypes.c_int()
-        _lib_mod.check(load().pbccs_scorer_is_favorable(self._h, ctypes.byref(m._c()), 1, ctypes.byref(f)))
-        return bool(f.value)
+    def IsFavorable(self, m, wide=False):
+        return self._favorable(m, 0, wide)
 
-    def ApplyMutations(self, muts):
+    def FastIsFavorable(self, m, wide=False):
+        return self._favorable(m, 1, wide)
+
+    def ApplyMutations(self, muts, wide=False):
+        if wide:
+            cs = [m._cx() for m in muts]
+            arr = (_lib_mod.CMutationEx * max(1, len(muts)))(*cs)
+            _lib_mod.check(load().pbccs_scorer_apply_mutations_ex(self._h, arr, len(muts)))
+            return
         arr = (_lib_mod.CMutation * max(1, len(muts)))(*[m._c() for m in muts])
         _lib_mod.check(load().pbccs_scorer_apply_mutations(self._h, arr, len(muts)))
 
@@ -304,8 +330,38 @@ from .polish import (ConsensusSettings, PreparedBatch, plan_batches, polish_many
 from . import quiver as _quiver  # noqa: E402
 from .quiver import (QvModelParams, QuiverConfig, QuiverConfigTable,  # noqa: E402,F401
                      QuiverMultiReadMutationScorer, QvEvaluator, QvSequenceFeatures, ALL_MOVES, BASIC_MOVES,
-                     RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator, RefineRepeats,
-                     RefineDinucleotideRepeats)
+                     RepeatMutationEnumerator, DinucleotideRepeatMutationEnumerator)
+
+
+def RefineRepeats(mms, repeat_length, min_repeat_elements=3, max_iterations=1, mutation_separation=10,
+                  mutation_neighborhood=20):
+    """RefineRepeats (Consensus.hpp:69-76): AbstractRefineConsensus over RepeatMutationEnumerator -> (converged, nT,
+    nA).  Templated on the scorer in the reference: Quiver scorers (quiver.RefineRepeats) or Arrow scorers
+    (pbccs_refine_repeats: k_score_wide, favourable = Score(m, FastScoreThreshold) > 0.04)."""
+    if isinstance(mms, _quiver.QuiverMultiReadMutationScorer):
+        return _quiver.RefineRepeats(mms, repeat_length, min_repeat_elements, max_iterations, mutation_separation,
+                                     mutation_neighborhood)
+    o = _lib_mod.CRepeatOptions(repeat_length, min_repeat_elements, max_iterations, mutation_separation,
+                                mutation_neighborhood)
+    nt, na, conv = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_int()
+    _lib_mod.check(load().pbccs_refine_repeats(mms._h, ctypes.byref(o), ctypes.byref(nt), ctypes.byref(na),
+                                               ctypes.byref(conv)))
+    return bool(conv.value), nt.value, na.value
+
+
+def RefineDinucleotideRepeats(mms, min_elements=3):
+    return RefineRepeats(mms, 2, min_elements)
+
+
+def wide_columns_needed(m, strand, template_start, template_end):
+    """The extension columns one read with window [template_start, template_end) on `strand` needs for mutation m
+    on the Arrow scorer's wide path (host only): -1 the read does not score it, 0 the whole-window refill, -2 the
+    mutated window would be empty; -2 and more than 8 are what the wide calls refuse."""
+    c = m._cx()
+    n = ctypes.c_int()
+    _lib_mod.check(load().pbccs_wide_columns_needed(ctypes.byref(c), int(strand), int(template_start),
+                                                    int(template_end), ctypes.byref(n)))
+    return n.value
 from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
 from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,

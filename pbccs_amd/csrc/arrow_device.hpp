@@ -254,6 +254,47 @@ __device__ inline VirtualMut make_virtual(const char* T, int L, int type, int s,
     return v;
 }
 
+// The wide view: the window of strand template T with T[ms, ms + nOld) replaced by nb new bases
+// (already on this strand; base k in byte k of `bases`, as QMutRec packs them), i.e. the window of
+// T' = T[0, ms) + bases + T[ms + nOld, L).  At() is TplView::Plain's rule applied to T': the base T'[g], the context
+// of (T'[g], T'[g + 1]) or the zero context at the last base.  Wherever the index lies inside the new length this
+// is what ApplyVirtualMutation's two slots give for a single-base mutation; Length() keeps VirtualLength's
+// condition, so width 1 reproduces TplView.
+struct TplViewWide {
+    const char* T;
+    int L;       // strand template length (unmutated)
+    int start;   // window start on this strand
+    int len;     // window length (unmutated)
+    int ms;      // mutation start on this strand (template coordinates)
+    int nOld;    // template bases replaced (0 for an insertion)
+    int nb;      // new bases (0 for a deletion)
+    unsigned long long bases;
+
+    __device__ __forceinline__ int Length() const
+    {
+        return (ms >= start && ms < start + len) ? len + (nb - nOld) : len;
+    }
+    __device__ __forceinline__ char BaseOf(int g) const   // T'[g]
+    {
+        if (g < ms) return T[g];
+        if (g < ms + nb) return (char)((bases >> (8 * (g - ms))) & 0xffull);
+        return T[g - nb + nOld];
+    }
+    __device__ __forceinline__ void At(int idx, char& b, int& c) const
+    {
+        const int g = idx + start;
+        b = BaseOf(g);
+        c = (g + 1 < L + nb - nOld) ? context_index(b, BaseOf(g + 1)) : kCtxZero;
+    }
+    __device__ __forceinline__ char Base(int idx) const { return BaseOf(idx + start); }
+    __device__ __forceinline__ int Ctx(int idx) const
+    {
+        char b; int c;
+        At(idx, b, c);
+        return c;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // Band matrix storage (ScaledSparseMatrixD semantics: cells outside a column's used row range read as
 // 0.0).  Alpha columns are stored top-down, beta columns bottom-up, each fill appending its cells in

@@ -8,54 +8,19 @@
 //                 (MutationEnumerator.cpp:114-145) + per-position offsets (for QVs).
 //   k_score       one lane per (mutation, read): MutationScorer::ScoreMutation - Score()
 //                 (MutationScorer.cpp:169-272) via register-only recompute sweeps.
+//                 (Its extend / link pieces are shared with arrow_wide_kernels.hip's k_score_wide, the scorer of
+//                 mutations of any width: arrow_score_device.hpp.)
 //   k_reduce      one lane per mutation: ordered per-read sum with the fast-score break
 //                 (MultiReadMutationScorer.cpp:338-368), favourable flag (> 0.04).
 //   k_qv          one lane per template position: ConsensusQVs (Consensus-inl.hpp:274-295).
 #include "arrow_device.hpp"
 #include "arrow_kernels.hpp"
+#include "arrow_score_device.hpp"
 #include "coop_chain.hpp"
 
 #include <climits>
 
 namespace pbccs {
-
-// ------------------------------------------------------------------------------------------------
-// helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ Params params_for(const DevBatch& B, int z)
-{
-    Params P;
-    P.ctx = B.zCtx + (long long)z * 9 * kCtxStride;
-    P.prNot = B.prNot;
-    P.prThird = B.prThird;
-    P.sdn = B.sdn;
-    return P;
-}
-
-__device__ __forceinline__ Band band_alpha(const DevBatch& B, int r)
-{
-    const long long cb = B.rColBase[r];
-    Band m;
-    m.range = B.aRange + cb;
-    m.off = B.aOff + cb;
-    m.ls = B.aLs + cb;
-    m.val = B.valPool + B.rValA[r];
-    m.cap = B.rValCap[r];
-    return m;
-}
-
-__device__ __forceinline__ Band band_beta(const DevBatch& B, int r)
-{
-    const long long cb = B.rColBase[r];
-    Band m;
-    m.range = B.bRange + cb;
-    m.off = B.bOff + cb;
-    m.ls = B.bLs + cb;
-    m.val = B.valPool + B.rValB[r];
-    m.cap = B.rValCap[r];
-    return m;
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // k_fill: FillAlphaBeta per read (MutationScorer ctor / Template(), MutationScorer.cpp:53-131), one
@@ -417,310 +382,8 @@ __global__ void __launch_bounds__(256) k_enumerate(DevBatch B, const int* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// Mutation scoring
+// Mutation scoring (ScoreCtx, extend_alpha_score and extend_beta_score: arrow_score_device.hpp)
 // ------------------------------------------------------------------------------------------------
-struct ScoreCtx {
-    const DevBatch* B;
-    Params P;
-    const char* rd;
-    int I;
-    int Jorig;   // unmutated window length (alpha/beta have Jorig + 1 columns)
-    TplView tv;
-    Band a, b;
-    const double* aPre;
-    const double* bSuf;
-};
-
-// ExtendAlpha (SimpleRecursor.cpp:373-487) over n <= 4 columns starting at `sc`, followed either by
-// LinkAlphaBeta (:306-357, n == 2, middle case) or by the at-end read-out (MutationScorer.cpp:219-231).
-// ext columns are never stored: sweep t recomputes columns 0..t-1 (scales known) and column t (its
-// max = the FinishEditingColumn constant); a final sweep produces the link sum.  Every recomputation
-// performs the same operations in the same order, so the values are bit-identical to a stored matrix.
-__device__ double extend_alpha_score(const ScoreCtx& S, int sc, int n, bool link, int bc, int absc, TaskStat& st)
-{
-    const int I = S.I;
-    const int Jv = S.tv.Length();
-    int cb[kMaxExtCols], ce[kMaxExtCols], jj[kMaxExtCols];
-    char cur[kMaxExtCols], nxt[kMaxExtCols];
-    double pM[kMaxExtCols], pD[kMaxExtCols], cB[kMaxExtCols], cS3[kMaxExtCols];
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c) {
-        cb[c] = 0; ce[c] = 0; jj[c] = 0; cur[c] = 0; nxt[c] = 0;
-        pM[c] = 0.0; pD[c] = 0.0; cB[c] = 0.0; cS3[c] = 0.0;
-        if (c < n) {
-            const int j = sc + c;
-            jj[c] = j;
-            int b, e;
-            if (j < Jv) {
-                const int2 r0 = S.a.range[j];
-                b = r0.x; e = r0.y;
-                if (j - 1 >= 0) { const int2 r1 = S.a.range[j - 1]; b = min(b, r1.x); e = max(e, r1.y); }
-                if (j + 1 < Jv) { const int2 r2 = S.a.range[j + 1]; b = min(b, r2.x); e = max(e, r2.y); }
-            } else {
-                b = S.a.range[S.Jorig].x;
-                e = I + 1;
-            }
-            cb[c] = b; ce[c] = e;
-            char cbase; int cctx;
-            S.tv.At(j - 1, cbase, cctx);
-            cur[c] = cbase;
-            const double* cp = S.P.P(cctx);
-            cB[c] = cp[kB]; cS3[c] = cp[kS3];
-            const int pctx = (j > 1) ? S.tv.Ctx(j - 2) : kCtxZero;
-            pM[c] = S.P.P(pctx)[kM];
-            pD[c] = S.P.P(pctx)[kD];
-            if (j != Jv) nxt[c] = S.tv.Base(j);
-        }
-    }
-    // alpha column sc-1 feeds ext column 0
-    const int2 ar = S.a.range[sc - 1];
-    const double* av = S.a.val + S.a.off[sc - 1] - ar.x;
-
-    // link setup
-    int lb = 0, le = 0;
-    char linkBase = 0;
-    double lM = 0.0, lD = 0.0;
-    int2 br = make_int2(0, 0);
-    const double* bv = nullptr;
-    if (link) {
-        lb = min(cb[0], cb[1]); le = max(ce[0], ce[1]);
-        const int2 b0 = S.b.range[bc], b1 = S.b.range[bc + 1];
-        lb = min(lb, min(b0.x, b1.x));
-        le = max(le, max(b0.y, b1.y));
-        linkBase = S.tv.Base(absc - 1);
-        const int lctx = S.tv.Ctx(absc - 2);
-        lM = S.P.P(lctx)[kM];
-        lD = S.P.P(lctx)[kD];
-        br = b0;
-        bv = S.b.val + S.b.off[bc] + (b0.y - 1);   // bv[-i] = beta(i, bc)
-    }
-
-    double C[kMaxExtCols], ls[kMaxExtCols];
-    bool scl[kMaxExtCols];
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c) { C[c] = 0.0; ls[c] = 0.0; scl[c] = false; }
-    double rawAtI = 0.0;
-    double v = 0.0;
-    const int nSweeps = link ? n + 1 : n;
-    for (int t = 0; t < nSweeps; ++t) {
-        const int top = min(t, n - 1);   // highest column computed in this sweep
-        int lo, hi;
-        if (t == n) { lo = lb; hi = le; }
-        else {
-            lo = cb[0]; hi = ce[0];
-#pragma unroll
-            for (int c = 1; c < kMaxExtCols; ++c)
-                if (c <= top) { lo = min(lo, cb[c]); hi = max(hi, ce[c]); }
-        }
-        double rawPrev[kMaxExtCols], scPrev[kMaxExtCols];
-#pragma unroll
-        for (int c = 0; c < kMaxExtCols; ++c) { rawPrev[c] = 0.0; scPrev[c] = 0.0; }
-        double Ct = 0.0;
-        for (int i = lo; i < hi; ++i) {
-            const double aD = (i - 1 >= ar.x && i - 1 < ar.y) ? av[i - 1] : 0.0;
-            const double aL = (i >= ar.x && i < ar.y) ? av[i] : 0.0;
-            const char rb = (i >= 1 && i - 1 < I) ? S.rd[i - 1] : (char)0;
-            double rawCur[kMaxExtCols], scCur[kMaxExtCols];
-#pragma unroll
-            for (int c = 0; c < kMaxExtCols; ++c) {
-                rawCur[c] = 0.0;
-                scCur[c] = 0.0;
-                if (c <= top) {
-                    const int j = jj[c];
-                    const double pd = (c == 0) ? aD : scPrev[c > 0 ? c - 1 : 0];
-                    const double pl = (c == 0) ? aL : scCur[c > 0 ? c - 1 : 0];
-                    double raw = 0.0;
-                    const bool in = (i >= cb[c] && i < ce[c]);
-                    if (in) {
-                        double s;
-                        if (i > 0 && j > 0) {
-                            const double em = (rb == cur[c]) ? S.P.prNot : S.P.prThird;
-                            double mv = 0.0;
-                            if (i == 1 && j == 1) mv = em;
-                            else if (i < I && j < Jv) mv = pd * pM[c] * em;
-                            else if (i == I && j == Jv) mv = pd * em;
-                            s = mv;
-                        } else {
-                            s = rawPrev[c];   // the reference's `score` carries over (never taken: i >= 1)
-                        }
-                        if (i > 1 && i < I && j != Jv) s = s + rawPrev[c] * (nxt[c] == rb ? cB[c] : cS3[c]);
-                        if (j > 1 && j < Jv && i != I) s = s + pl * pD[c];
-                        raw = s;
-                    }
-                    rawCur[c] = raw;
-                    if (c < t) {
-                        scCur[c] = in ? (scl[c] ? raw / C[c] : raw) : 0.0;
-                    } else if (in) {   // c == t < n: the column whose scale this sweep determines
-                        if (Ct < raw) Ct = raw;
-                        if (i == I) rawAtI = raw;
-                    }
-                }
-            }
-            if (t == n) {
-                const double s1 = scCur[1];
-                if (i < I) {
-                    const double mprob = lM * (S.rd[i] == linkBase ? S.P.prNot : S.P.prThird);
-                    const double bn = (i + 1 >= br.x && i + 1 < br.y) ? bv[-(i + 1)] : 0.0;
-                    v = v + s1 * mprob * bn;
-                }
-                const double bh = (i >= br.x && i < br.y) ? bv[-i] : 0.0;
-                v = v + s1 * lD * bh;
-            }
-#pragma unroll
-            for (int c = 0; c < kMaxExtCols; ++c) { rawPrev[c] = rawCur[c]; scPrev[c] = scCur[c]; }
-        }
-        if (t < n) {
-#pragma unroll
-            for (int c = 0; c < kMaxExtCols; ++c)
-                if (c == t) {
-                    C[c] = Ct;
-                    scl[c] = (Ct != 0.0 && Ct != 1.0);
-                    ls[c] = scl[c] ? log(Ct) : 0.0;
-                }
-        }
-    }
-    double E = 0.0;
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c)
-        if (c < n) {
-            E = E + ls[c];
-            st.cells += (unsigned long long)max(0, ce[c] - cb[c]);
-        }
-    st.bytes += 8ull * (unsigned long long)max(0, ar.y - ar.x) + 16ull * (unsigned long long)(n + 2);
-    if (link) {
-        st.cells += (unsigned long long)max(0, le - lb);
-        st.bytes += 8ull * (unsigned long long)max(0, br.y - br.x) + 32ull;
-        return ((log(v) + E) + S.bSuf[bc]) + S.aPre[sc];
-    }
-    // at-end read-out: ext(I, n-1)
-    double lastC = 0.0, lastRange = 0.0;
-    bool lastScl = false;
-    int lastB = 0, lastE = 0;
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c)
-        if (c == n - 1) { lastC = C[c]; lastScl = scl[c]; lastB = cb[c]; lastE = ce[c]; }
-    (void)lastRange;
-    double extI = 0.0;
-    if (I >= lastB && I < lastE) extI = lastScl ? rawAtI / lastC : rawAtI;
-    return (log(extI) + S.aPre[sc]) + E;
-}
-
-// ExtendBeta (SimpleRecursor.cpp:509-628) back to column 0 for mutations near the template start,
-// read out as in MutationScorer.cpp:233-245.  Columns are filled high to low, rows bottom-up.
-__device__ double extend_beta_score(const ScoreCtx& S, int lastCol, int ld, TaskStat& st)
-{
-    const int I = S.I;
-    const int Jv = S.tv.Length();
-    const int nExt = ld + lastCol + 1;
-    const int firstCol = -ld;
-    const int lastExt = nExt - 1;
-    int cb[kMaxExtCols], ce[kMaxExtCols], jj[kMaxExtCols], jpv[kMaxExtCols];
-    char nxt[kMaxExtCols];
-    double cM[kMaxExtCols], cD[kMaxExtCols], cB[kMaxExtCols], cS3[kMaxExtCols];
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c) {
-        cb[c] = 0; ce[c] = 0; jj[c] = 0; jpv[c] = 0; nxt[c] = 0;
-        cM[c] = 0.0; cD[c] = 0.0; cB[c] = 0.0; cS3[c] = 0.0;
-        if (c < nExt) {
-            const int j = c + firstCol;
-            const int jp = j + ld;
-            jj[c] = j; jpv[c] = jp;
-            int b, e;
-            if (j < 0) {
-                b = 0;
-                e = S.b.range[0].y;
-            } else {
-                const int2 r0 = S.b.range[j];
-                b = r0.x; e = r0.y;
-                if (j - 1 >= 0) { const int2 r1 = S.b.range[j - 1]; b = min(b, r1.x); e = max(e, r1.y); }
-                if (j + 1 < Jv) { const int2 r2 = S.b.range[j + 1]; b = min(b, r2.x); e = max(e, r2.y); }
-            }
-            cb[c] = b; ce[c] = e;
-            nxt[c] = S.tv.Base(jp);
-            const int cctx = (jp > 0) ? S.tv.Ctx(jp - 1) : kCtxZero;
-            const double* cp = S.P.P(cctx);
-            cM[c] = cp[kM]; cD[c] = cp[kD]; cB[c] = cp[kB]; cS3[c] = cp[kS3];
-        }
-    }
-    // beta column lastCol + 1 feeds ext column lastExt
-    const int2 br = S.b.range[lastCol + 1];
-    const double* bv = S.b.val + S.b.off[lastCol + 1] + (br.y - 1);   // bv[-i] = beta(i, lastCol+1)
-
-    double C[kMaxExtCols], ls[kMaxExtCols];
-    bool scl[kMaxExtCols];
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c) { C[c] = 0.0; ls[c] = 0.0; scl[c] = false; }
-    double rawAt0 = 0.0;
-    for (int t = lastExt; t >= 0; --t) {
-        int lo = cb[lastExt], hi = ce[lastExt];
-#pragma unroll
-        for (int c = 0; c < kMaxExtCols; ++c)
-            if (c >= t && c < nExt) { lo = min(lo, cb[c]); hi = max(hi, ce[c]); }
-        double rawPrev[kMaxExtCols], scPrev[kMaxExtCols];   // values at row i+1
-#pragma unroll
-        for (int c = 0; c < kMaxExtCols; ++c) { rawPrev[c] = 0.0; scPrev[c] = 0.0; }
-        double Ct = 0.0;
-        for (int i = hi - 1; i >= lo; --i) {
-            const double bN = (i + 1 >= br.x && i + 1 < br.y) ? bv[-(i + 1)] : 0.0;   // beta(i+1, lastCol+1)
-            const double bH = (i >= br.x && i < br.y) ? bv[-i] : 0.0;                 // beta(i, lastCol+1)
-            const char nb = (i < I) ? S.rd[i] : 'N';
-            double rawCur[kMaxExtCols], scCur[kMaxExtCols];
-#pragma unroll
-            for (int c = 0; c < kMaxExtCols; ++c) { rawCur[c] = 0.0; scCur[c] = 0.0; }
-#pragma unroll
-            for (int cc = kMaxExtCols - 1; cc >= 0; --cc) {
-                if (cc >= t && cc < nExt) {
-                    const int j = jj[cc], jp = jpv[cc];
-                    const double nxD = (cc == lastExt) ? bN : scPrev[cc + 1 < kMaxExtCols ? cc + 1 : cc];
-                    const double nxH = (cc == lastExt) ? bH : scCur[cc + 1 < kMaxExtCols ? cc + 1 : cc];
-                    const bool in = (i >= cb[cc] && i < ce[cc]);
-                    double raw = 0.0;
-                    if (in) {
-                        const bool same = nb == nxt[cc];
-                        double s = 0.0;
-                        if (i < I && j < Jv) {
-                            const double em = same ? S.P.prNot : S.P.prThird;
-                            double mv = 0.0;
-                            if ((i == I - 1 && jp == Jv - 1) || (i == 0 && j == firstCol)) mv = nxD * em;
-                            else if (j > firstCol && i > 0) mv = nxD * cM[cc] * em;
-                            s = 0.0 + mv;
-                        }
-                        if (i < I - 1 && i > 0 && j > firstCol) s = s + rawPrev[cc] * (same ? cB[cc] : cS3[cc]);
-                        if (j < Jv - 1 && j > firstCol && i > 0) s = s + nxH * cD[cc];
-                        raw = s;
-                    }
-                    rawCur[cc] = raw;
-                    if (cc > t) {
-                        scCur[cc] = in ? (scl[cc] ? raw / C[cc] : raw) : 0.0;
-                    } else if (in) {
-                        if (Ct < raw) Ct = raw;
-                        if (i == 0) rawAt0 = raw;
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < kMaxExtCols; ++c) { rawPrev[c] = rawCur[c]; scPrev[c] = scCur[c]; }
-        }
-#pragma unroll
-        for (int c = 0; c < kMaxExtCols; ++c)
-            if (c == t) {
-                C[c] = Ct;
-                scl[c] = (Ct != 0.0 && Ct != 1.0);
-                ls[c] = scl[c] ? log(Ct) : 0.0;
-            }
-    }
-    double E = 0.0;
-#pragma unroll
-    for (int c = 0; c < kMaxExtCols; ++c)
-        if (c < nExt) {
-            E = E + ls[c];
-            st.cells += (unsigned long long)max(0, ce[c] - cb[c]);
-        }
-    st.bytes += 8ull * (unsigned long long)max(0, br.y - br.x) + 16ull * (unsigned long long)(nExt + 2);
-    const double ext00 = (0 >= cb[0] && 0 < ce[0]) ? (scl[0] ? rawAt0 / C[0] : rawAt0) : 0.0;
-    return (log(ext00) + S.bSuf[lastCol + 1]) + E;
-}
-
 __device__ __forceinline__ bool read_scores(int ts, int te, int type, int ms, int me)
 {
     if (type == kIns) return ts <= me && ms <= te;   // MultiReadMutationScorer.cpp:70-80
@@ -918,12 +581,12 @@ __device__ double score_edge(const ScoreCtx& S, const Oriented& o, const ScoreSc
     if (!atBegin && atEnd) {
         const int sc = o.os - 1;
         const int n = S.tv.Length() - sc + 1;
-        return extend_alpha_score(S, sc, n, false, 0, 0, st);
+        return extend_alpha_score<TplView, kMaxExtCols>(S, sc, n, false, 0, 0, st);
     }
-    if (atBegin && !atEnd) return extend_beta_score(S, o.oe, o.ld, st);
+    if (atBegin && !atEnd) return extend_beta_score<TplView, kMaxExtCols>(S, o.oe, o.ld, st);
     if (!atBegin && !atEnd) {   // not reached from k_score (middle case has its own path)
         const int sc = (o.type == kDel) ? o.os - 1 : o.os;
-        return extend_alpha_score(S, sc, 2, true, 1 + o.oe, 1 + o.oe + o.ld, st);
+        return extend_alpha_score<TplView, kMaxExtCols>(S, sc, 2, true, 1 + o.oe, 1 + o.oe + o.ld, st);
     }
     // whole fill of the virtually mutated window (MutationScorer.cpp:246-266); tiny windows only
     const int Jv = S.tv.Length();

@@ -66,6 +66,26 @@ struct ScoreScratch {
     int* overflow = nullptr;
 };
 
+// One (mutation, read) task of k_score_wide (arrow_wide_kernels.hip): the mutation oriented and
+// clipped for the read (OrientedMutation), in the coordinates of the read's window on its strand.
+struct WideTask {
+    int r;       // read
+    int type;    // MutType
+    int os, oe;  // the window columns [os, oe) the mutation replaces
+    int nb;      // new bases (0 for a deletion)
+    int slot;    // delta[slot] receives ScoreMutation - Score()
+    unsigned long long bases;   // the new bases on the read's strand, base k in byte k
+};
+constexpr int kWideMaxBases = 7;    // PBCCS_MAX_MUTATION_BASES
+constexpr int kWideExtColumns = 8;  // extension columns k_score_wide holds
+constexpr int kWideRefillWidth = 3; // mutations this wide or wider are scored by a refill of the window
+// A task k_score_wide_refill scores: ScoreMutation's whole-fill case (both window ends within three columns), or a
+// mutation kWideRefillWidth or more bases wide; every other task is k_score_wide's.
+__host__ __device__ inline bool wide_task_refills(int os, int oe, int nb, int J)
+{
+    return (os < 3 && oe > J - 2) || (nb > oe - os ? nb : oe - os) >= kWideRefillWidth;
+}
+
 // Lane-interleaved fill scratch: group g (64 reads) x matrix (alpha, beta) x slot/column x lane.
 struct FillScratch {
     double* val = nullptr;    // [2G][capSlots][64]
@@ -148,6 +168,13 @@ void launch_alive(const DevBatch& B, const ScoreWork& W, long long nMut, double 
                   unsigned char* alive, hipStream_t s);
 void launch_sel_ranges(const ScoreWork& W, const long long* sel, const long long* count, long long* selBase,
                        int* nSel, hipStream_t s);
+// k_score_wide over a task list; delta[task.slot] = ScoreMutation - Score().
+void launch_score_wide(const DevBatch& B, const WideTask* tasks, int n, double* delta, hipStream_t s);
+// k_score_wide_refill over the tasks wide_task_refills() names.  rowsCap: values per column (on average) a refill's
+// band may take; a refill that needs more sets bit 4 of scratch.overflow and leaves NaN, a full pool sets bit 1 (the
+// host grows either and reruns the launch).
+void launch_score_wide_refill(const DevBatch& B, const WideTask* tasks, int n, double* delta,
+                              const ScoreScratch& scratch, int rowsCap, hipStream_t s);
 void launch_reduce(const DevBatch& B, const ScoreWork& W, long long nMut, double fastThr, double* score,
                    unsigned char* fav, hipStream_t s);
 // BestSubset (Consensus-inl.hpp:98-118) on the compacted favourable list: one wavefront per work item over

@@ -316,6 +316,44 @@ void nearby_repeat_mutations(const std::string& tpl, int repeatLength, int minRe
     out->insert(out->end(), all.begin(), all.end());
 }
 
+OrientedEx orient_mutation_ex(const MutationEx& m, int strand, int ts, int te)
+{
+    OrientedEx o;
+    o.type = m.type;
+    o.scores = m.type == 0 ? (ts <= m.end && m.start <= te) : (ts < m.end && m.start < te);
+    if (!o.scores) return o;
+    int cs = m.start, ce = m.end;
+    std::string bases = m.bases;
+    if (m.end - m.start > 1) {
+        cs = std::max(m.start, ts);
+        ce = std::min(m.end, te);
+        if (m.type == 2) bases = m.bases.substr((size_t)(cs - m.start), (size_t)(ce - cs));
+    }
+    if (strand == 0) {
+        o.os = cs - ts;
+        o.oe = ce - ts;
+        o.bases = bases;
+    } else {
+        o.os = te - ce;
+        o.oe = te - cs;
+        o.bases = reverse_complement(bases);
+    }
+    return o;
+}
+
+int wide_columns_needed(const OrientedEx& o, int J)
+{
+    const int ld = o.LengthDiff();
+    // VirtualLength (TemplateParameterPair.hpp:120-127): the length changes only when the start lies in the window
+    const int Jv = (o.os >= 0 && o.os < J) ? J + ld : J;
+    if (Jv < 1) return -1;
+    const bool atBegin = o.os < 3, atEnd = o.oe > J - 2;
+    if (!atBegin && !atEnd) return o.type == 1 ? 2 : 1 + (int)o.bases.size();
+    if (!atBegin) return Jv - (o.os - 1) + 1;
+    if (!atEnd) return o.oe + ld + 1;
+    return 0;
+}
+
 int probability_to_qv(double p)
 {
     if (p < 0.0 || p > 1.0) throw std::invalid_argument("invalid value: probability not in [0,1]");

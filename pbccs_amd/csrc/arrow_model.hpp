@@ -118,6 +118,23 @@ void repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatEle
 void nearby_repeat_mutations(const std::string& tpl, int repeatLength, int minRepeatElements,
                              const std::vector<int>& centerStarts, int nbhd, std::vector<MutationEx>* out);
 
+// Arrow's view of a mutation of any width from one read: ReadScoresMutation
+// (Arrow/MultiReadMutationScorer.cpp:70-80), then OrientedMutation (:93-139) -- the clip to the read's window for
+// mutations wider than one template base, then the strand -- in the coordinates of the window [ts, te).
+struct OrientedEx {
+    bool scores = false;   // the read scores the mutation
+    int type = 2;
+    int os = 0, oe = 0;    // the window columns [os, oe) replaced, on the read's strand
+    std::string bases;     // the new bases on the read's strand (clipped for a substitution)
+    int LengthDiff() const { return type == 0 ? (int)bases.size() : (type == 1 ? os - oe : 0); }
+};
+OrientedEx orient_mutation_ex(const MutationEx& m, int strand, int ts, int te);
+// Extension columns ScoreMutation (Arrow/MutationScorer.cpp:185-267) needs for an oriented mutation in a window of J
+// columns: 1 + |bases| in the middle (2 for a deletion), to the window's end or its start in the edge cases, 0 for
+// the whole-window refill (it takes a band from scratch, not the extension buffer), -1 when the mutated window
+// would be empty.
+int wide_columns_needed(const OrientedEx& o, int J);
+
 // ProbabilityToQV (Consensus-inl.hpp:130-138)
 int probability_to_qv(double p);
 

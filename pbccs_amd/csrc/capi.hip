@@ -55,6 +55,7 @@ struct pbccs_engine {
     int nextSlot = 0;
     std::mutex statsMu;        // counters / stats are merged from the slots' worker threads
     long long oomRetries = 0;   // device batches rerun after PBCCS_EOOM
+    long long repeatSkippedCkpt = 0;   // pbccs_polish_batch_ex: ZMWs whose repeat round a checkpointed read skipped
     DiploidStats diploid;       // the diploid screen's work (pbccs_diploid_stats_get)
     long long createHostNs = 0, createUploadNs = 0;   // pbccs_batch_create: host setup / reservations + upload
     std::vector<std::unique_ptr<Workspace>> slots;
@@ -197,6 +198,9 @@ struct pbccs_batch {
     std::vector<std::vector<unsigned char>> fullPass;
     std::vector<int> allReads;
     bool polished = false;
+    // pbccs_polish_batch_ex: RefineRepeats between RefineConsensus and ConsensusQVs
+    bool hasRepeats = false;
+    pbccs_repeat_options repeats{};
 };
 
 struct pbccs_scorer {
@@ -320,9 +324,11 @@ int pbccs_engine_counters(pbccs_engine* eng, pbccs_counters* out, int reset)
     out->uncertain_reads = eng->counters.uncertainReads;
     out->exact_rounds = eng->counters.exactRounds;
     for (int k = 0; k < 4; ++k) out->uncertain_why[k] = eng->counters.uncertainWhy[k];
+    out->repeat_skipped_ckpt = eng->repeatSkippedCkpt;
     if (reset) {
         eng->counters = Counters();
         eng->oomRetries = 0;
+        eng->repeatSkippedCkpt = 0;
         eng->createHostNs = eng->createUploadNs = 0;
     }
     return PBCCS_OK;
@@ -573,7 +579,7 @@ static void merge_engine_stats(pbccs_engine* eng, ArrowBatch& B)
 
 // A batch on an explicit workspace slot (slot < 0: the next slot round-robin).
 static int create_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
-                        int slot, pbccs_batch** out)
+                        int slot, pbccs_batch** out, const pbccs_repeat_options* repeats = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && !in) || !out) return fail(PBCCS_EINVAL, "bad argument");
     return guarded([&] {
@@ -584,6 +590,10 @@ static int create_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, con
         pbccs_polish_options_default(&b->o);
         if (opts) b->o = *opts;
         b->n = n;
+        if (repeats) {
+            b->hasRepeats = true;
+            b->repeats = *repeats;
+        }
         b->slot = slot >= 0 ? slot : eng->nextSlot++ % std::max(1, eng->concurrency);
         b->inputs.assign(in, n);
         // every batch gets its own streams (ArrowBatch's ownStreams); a batch made and polished on its slot's thread
@@ -640,7 +650,9 @@ int pbccs_batch_create(pbccs_engine* eng, const pbccs_zmw_input* in, int n, cons
 
 void pbccs_batch_destroy(pbccs_batch* b) { delete b; }
 
-static int polish_one(pbccs_batch* b, pbccs_zmw_output* out)
+// repTested / repApplied (b->n entries each, may be NULL): RefineRepeats' counts of a batch made with repeats
+static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTested = nullptr,
+                      long long* repApplied = nullptr)
 {
     if (!b || (b->n > 0 && !out)) return fail(PBCCS_EINVAL, "bad argument");
     if (b->polished) return fail(PBCCS_ESTATE, "a batch polishes once");
@@ -670,11 +682,13 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out)
         // converges.  Opt-in: it cuts the refine rounds' band top (42.5 -> 39.9 GB per 2000-ZMW batch; the
         // initial fill sets the high-water) but the per-round QVs cost 5.5% (profiles/r2h5_reclaim_ab)
         const char* reclaimEnv = std::getenv("PBCCS_RECLAIM");
-        const bool reclaim = reclaimEnv && std::strcmp(reclaimEnv, "1") == 0;
+        // (the repeat round reads the converged ZMWs' bands after the refine loop: no reclaim with it)
+        const bool reclaim = reclaimEnv && std::strcmp(reclaimEnv, "1") == 0 && !b->hasRepeats;
         B.SetReclaim(reclaim);
         // the certified fast path for the batch's tall reads; PBCCS_CERTIFIED_SCAN=0: exact fills only
         const char* ce = std::getenv("PBCCS_CERTIFIED_SCAN");   // read per batch: tests switch it at run time
-        const bool certified = !ce || ce[0] != '0';
+        // (k_score_wide's scores carry no deviation bound: a batch with a repeat round fills exactly)
+        const bool certified = (!ce || ce[0] != '0') && !b->hasRepeats;
         B.SetCertifiedScan(certified);
         B.FillReads(b->allReads);
         B.CertifyAddReads(b->allReads, o.min_zscore);
@@ -736,6 +750,41 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out)
                 if (reclaim) qvs.push_back(std::move(qvAll[k]));
             } else q.status = conv[k] < 0 ? PBCCS_ZMW_OTHER : PBCCS_ZMW_NON_CONVERGENT;
         }
+        for (int i = 0; i < n; ++i) {
+            if (repTested) repTested[i] = 0;
+            if (repApplied) repApplied[i] = 0;
+        }
+        if (b->hasRepeats && !qvZ.empty()) {
+            // RefineRepeats on the ZMWs RefineConsensus converged on, in lock-step rounds; a ZMW with a read on
+            // checkpointed bands skips it (status 3) and finishes as it would without the repeat round
+            RefineOptions rr;
+            rr.maxIterations = b->repeats.max_iterations;
+            rr.mutationSeparation = b->repeats.mutation_separation;
+            rr.mutationNeighborhood = b->repeats.mutation_neighborhood;
+            std::vector<long long> rt, ra;
+            std::vector<char> rconv;
+            std::vector<int> rst;
+            B.RefineRepeats(qvZ, b->repeats.repeat_length, b->repeats.min_repeat_elements, rr, &rt, &ra, &rconv, &rst);
+            std::vector<int> keepZ, keepIdx;
+            long long skipped = 0;
+            for (size_t k = 0; k < qvZ.size(); ++k) {
+                if (repTested) repTested[qvIdx[k]] = rt[k];
+                if (repApplied) repApplied[qvIdx[k]] = ra[k];
+                if (rst[k] == 3) ++skipped;
+                if (rst[k] == 1 || rst[k] == 2) {
+                    out[qvIdx[k]].status = PBCCS_ZMW_OTHER;
+                    continue;
+                }
+                keepZ.push_back(qvZ[k]);
+                keepIdx.push_back(qvIdx[k]);
+            }
+            qvZ.swap(keepZ);
+            qvIdx.swap(keepIdx);
+            if (skipped) {
+                std::lock_guard<std::mutex> lk(b->eng->statsMu);
+                b->eng->repeatSkippedCkpt += skipped;
+            }
+        }
         if (!reclaim) B.QVs(qvZ, &qvs);
         for (size_t k = 0; k < qvZ.size(); ++k) {
             pbccs_zmw_output& q = out[qvIdx[k]];
@@ -760,11 +809,12 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out)
 
 // Create, polish, account and destroy one device batch of m ZMWs on `slot`.
 static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int m, const pbccs_polish_options* o,
-                       pbccs_zmw_output* out)
+                       pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
+                       long long* repTested = nullptr, long long* repApplied = nullptr)
 {
     pbccs_batch* h = nullptr;
-    int r = create_batch(eng, in, m, o, slot, &h);
-    if (r == PBCCS_OK) r = polish_one(h, out);
+    int r = create_batch(eng, in, m, o, slot, &h, repeats);
+    if (r == PBCCS_OK) r = polish_one(h, out, repTested, repApplied);
     if (h) {
         if (h->B) merge_engine_stats(eng, *h->B);
         pbccs_batch_destroy(h);
@@ -777,7 +827,8 @@ static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, i
 // not depend on the batch it polishes in (the engine's only cross-ZMW state is the launch grouping), so
 // the retry changes the schedule and nothing else.  Outputs land in out[0..n) in input order.
 static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int n, const pbccs_polish_options* o,
-                        pbccs_zmw_output* out)
+                        pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
+                        long long* repTested = nullptr, long long* repApplied = nullptr)
 {
     std::vector<std::pair<int, int>> todo{{0, n}};
     // the slot's outgrown buffers go back to the device before the rerun (nothing of the slot is queued: its batches
@@ -790,7 +841,9 @@ static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, 
             std::lock_guard<std::mutex> lk(eng->statsMu);
             eng->oomRetries += 1;
         }
-        const int r = polish_span(eng, slot, in + span.first, span.second - span.first, o, out + span.first);
+        const int r = polish_span(eng, slot, in + span.first, span.second - span.first, o, out + span.first, repeats,
+                                  repTested ? repTested + span.first : nullptr,
+                                  repApplied ? repApplied + span.first : nullptr);
         if (r == PBCCS_OK) continue;
         if (r != PBCCS_EOOM || span.second - span.first < 2) return r;
         eng->Slot(slot)->val.unmap_all();
@@ -995,8 +1048,10 @@ int pbccs_plan_batches(const pbccs_zmw_input* in, int n, double budget_bytes, in
     return PBCCS_OK;
 }
 
-int pbccs_polish_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
-                       pbccs_zmw_output* out)
+// pbccs_polish_batch (repeats == NULL) and pbccs_polish_batch_ex: the ZMW work queue
+static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                             const pbccs_repeat_options* repeats, long long* repTested, long long* repApplied,
+                             pbccs_zmw_output* out)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
     if (n == 0) return PBCCS_OK;
@@ -1052,6 +1107,13 @@ int pbccs_polish_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, cons
     auto scatter = [&](int b, int e, const std::vector<pbccs_zmw_output>& bout) {
         for (int k = 0; k < e - b; ++k) out[order[b + k]] = bout[k];
     };
+    // RefineRepeats' counts of a span, back to input order
+    auto scatter_counts = [&](int b, int e, const std::vector<long long>& rt, const std::vector<long long>& ra) {
+        for (int k = 0; k < e - b; ++k) {
+            if (repTested) repTested[order[b + k]] = rt[k];
+            if (repApplied) repApplied[order[b + k]] = ra[k];
+        }
+    };
     // Batches that ran the device out of memory while the other slots held theirs are deferred and rerun
     // one at a time once every slot's pool is unmapped (polish_retry).
     std::mutex deferMu;
@@ -1059,18 +1121,26 @@ int pbccs_polish_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, cons
     auto worker = [&](int slot) {
         std::vector<pbccs_zmw_input> bin;
         std::vector<pbccs_zmw_output> bout;
+        std::vector<long long> brt, bra;
         for (;;) {
             const int b = next.fetch_add(1);
             if (b >= nb || stop.load()) return;
             int r = PBCCS_OK;
             try {
                 gather(start[b], start[b + 1], &bin, &bout);
+                if (repeats) {
+                    brt.assign(start[b + 1] - start[b], 0);
+                    bra.assign(start[b + 1] - start[b], 0);
+                }
             } catch (...) {
                 r = fail(PBCCS_EOOM, "out of host memory");
             }
-            if (r == PBCCS_OK) r = polish_span(eng, slot, bin.data(), start[b + 1] - start[b], &o, bout.data());
+            if (r == PBCCS_OK)
+                r = polish_span(eng, slot, bin.data(), start[b + 1] - start[b], &o, bout.data(), repeats,
+                                repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr);
             if (r == PBCCS_OK) {
                 scatter(start[b], start[b + 1], bout);
+                if (repeats) scatter_counts(start[b], start[b + 1], brt, bra);
             } else if (r == PBCCS_EOOM) {
                 std::lock_guard<std::mutex> lk(deferMu);
                 deferred.emplace_back(start[b], start[b + 1]);
@@ -1101,14 +1171,33 @@ int pbccs_polish_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, cons
             std::vector<pbccs_zmw_output> bout;
             for (const std::pair<int, int>& span : deferred) {
                 gather(span.first, span.second, &bin, &bout);
-                const int r = polish_retry(eng, 0, bin.data(), span.second - span.first, &o, bout.data());
+                std::vector<long long> brt(span.second - span.first, 0), bra(span.second - span.first, 0);
+                const int r = polish_retry(eng, 0, bin.data(), span.second - span.first, &o, bout.data(), repeats,
+                                           repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr);
                 if (r != PBCCS_OK) return r;
                 scatter(span.first, span.second, bout);
+                if (repeats) scatter_counts(span.first, span.second, brt, bra);
             }
             return PBCCS_OK;
         });
     }
     return PBCCS_OK;
+}
+
+int pbccs_polish_batch(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                       pbccs_zmw_output* out)
+{
+    return polish_batch_impl(eng, in, n, opts, nullptr, nullptr, nullptr, out);
+}
+
+int pbccs_polish_batch_ex(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                          const pbccs_repeat_options* repeats, long long* repeat_tested, long long* repeat_applied,
+                          pbccs_zmw_output* out)
+{
+    if (repeats && (repeats->repeat_length < 1 || repeats->repeat_length > PBCCS_MAX_MUTATION_BASES))
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return polish_batch_impl(eng, in, n, opts, repeats, repeats ? repeat_tested : nullptr,
+                             repeats ? repeat_applied : nullptr, out);
 }
 
 int pbccs_engine_set_profiling(pbccs_engine* eng, int on)
@@ -1504,6 +1593,119 @@ int pbccs_apply_mutations(const char* tpl, int tpl_len, const pbccs_mutation_ex*
     if ((int)next.size() + 1 > cap) return fail(PBCCS_ERANGE, "buffer too small");
     std::memcpy(out, next.c_str(), next.size() + 1);
     if (mtp) std::copy(map.begin(), map.end(), mtp);
+    return PBCCS_OK;
+}
+
+// ---- Arrow: mutations of any width ---------------------------------------------------
+// the scoring calls' common front: parse (ACGT only), the checkpoint refusal, then the 8-column rule -- all on
+// the host, before any launch
+static int arrow_scorable_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int n, std::vector<MutationEx>* out)
+{
+    for (int i = 0; i < n; ++i) {
+        MutationEx mu;
+        if (!to_mutation_ex(m[i], true, false, &mu)) return fail(PBCCS_EINVAL, "invalid multi-base mutation");
+        out->push_back(mu);
+    }
+    if (s->batch->HasCheckpointedReads(s->z))
+        return fail(PBCCS_EINVAL, "a read keeps checkpointed bands: wide mutations are not scored on this scorer");
+    std::string why;
+    if (!s->batch->WideColumnsFit(s->z, *out, &why)) return fail(PBCCS_EINVAL, why.c_str());
+    return PBCCS_OK;
+}
+
+int pbccs_scorer_score_many_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int n, double fast_threshold,
+                               double* scores)
+{
+    if (!s || n < 0 || (n > 0 && (!m || !scores))) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<std::vector<MutationEx>> muts(1);
+        if (arrow_scorable_ex(s, m, n, &muts[0]) != PBCCS_OK) return PBCCS_EINVAL;
+        if (n == 0) return PBCCS_OK;
+        std::vector<std::vector<double>> sc;
+        s->batch->ScoreWide({s->z}, muts, fast_threshold, &sc);
+        for (int i = 0; i < n; ++i) scores[i] = sc[0][i];
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_scorer_scores_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, double unscored, double* per_read)
+{
+    if (!s || !m || !per_read) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<std::vector<MutationEx>> muts(1);
+        if (arrow_scorable_ex(s, m, 1, &muts[0]) != PBCCS_OK) return PBCCS_EINVAL;
+        std::vector<std::vector<double>> sc, pr;
+        s->batch->ScoreWide({s->z}, muts, -std::numeric_limits<double>::max(), &sc, &pr);
+        const int nr = s->batch->NumReads(s->z);
+        for (int k = 0; k < nr; ++k) per_read[k] = std::isnan(pr[0][k]) ? unscored : pr[0][k];
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_scorer_is_favorable_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int fast, int* favorable)
+{
+    if (!s || !m || !favorable) return fail(PBCCS_EINVAL, "bad argument");
+    double v = 0.0;
+    const double thr = fast ? s->cfg.fast_score_threshold : -std::numeric_limits<double>::max();
+    const int rc = pbccs_scorer_score_many_ex(s, m, 1, thr, &v);
+    if (rc != PBCCS_OK) return rc;
+    *favorable = v > kMinFavorableScoreDiff ? 1 : 0;
+    return PBCCS_OK;
+}
+
+int pbccs_scorer_apply_mutations_ex(pbccs_scorer* s, const pbccs_mutation_ex* m, int n)
+{
+    if (!s || n < 0 || (n > 0 && !m)) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<MutationEx> muts;
+        for (int i = 0; i < n; ++i) {
+            MutationEx mu;
+            if (!to_mutation_ex(m[i], true, false, &mu)) return fail(PBCCS_EINVAL, "invalid multi-base mutation");
+            muts.push_back(mu);
+        }
+        if (!s->batch->ApplyMutationsEx(s->z, muts))
+            return fail(PBCCS_EINVAL, "mutation outside the template, or overlapping edits");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_refine_repeats(pbccs_scorer* s, const pbccs_repeat_options* opts, long long* n_tested, long long* n_applied,
+                         int* converged)
+{
+    if (!s || !n_tested || !n_applied || !converged) return fail(PBCCS_EINVAL, "bad argument");
+    pbccs_repeat_options o = {2, 3, 1, 10, 20};
+    if (opts) o = *opts;
+    if (o.repeat_length < 1 || o.repeat_length > PBCCS_MAX_MUTATION_BASES)
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return guarded([&] {
+        RefineOptions ro;
+        ro.maxIterations = o.max_iterations;
+        ro.mutationSeparation = o.mutation_separation;
+        ro.mutationNeighborhood = o.mutation_neighborhood;
+        std::vector<long long> nt, na;
+        std::vector<char> conv;
+        std::vector<int> st;
+        s->batch->RefineRepeats({s->z}, o.repeat_length, o.min_repeat_elements, ro, &nt, &na, &conv, &st);
+        *n_tested = nt[0];
+        *n_applied = na[0];
+        if (st[0] == 1) return fail(PBCCS_EINVAL, "invalid edit");
+        if (st[0] == 2) return fail(PBCCS_EINVAL, "repeat mutation needs more than 8 extension columns on some read");
+        if (st[0] == 3)
+            return fail(PBCCS_EINVAL, "a read keeps checkpointed bands: wide mutations are not scored on this scorer");
+        *converged = conv[0] ? 1 : 0;
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_wide_columns_needed(const pbccs_mutation_ex* m, int strand, int tstart, int tend, int* columns)
+{
+    if (!m || !columns || (strand != 0 && strand != 1) || tstart < 0 || tend < tstart)
+        return fail(PBCCS_EINVAL, "bad argument");
+    MutationEx mu;
+    if (!to_mutation_ex(*m, true, false, &mu)) return fail(PBCCS_EINVAL, "invalid multi-base mutation");
+    const OrientedEx o = orient_mutation_ex(mu, strand, tstart, tend);
+    const int c = o.scores ? wide_columns_needed(o, tend - tstart) : 0;
+    *columns = !o.scores ? -1 : (c < 0 ? -2 : c);
     return PBCCS_OK;
 }
 

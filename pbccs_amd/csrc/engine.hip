@@ -1,6 +1,7 @@
 // pbccs_amd/csrc/engine.hip -- ArrowBatch: HBM residency + orchestration of the polishing rounds.
 #include "engine.hpp"
 #include "diploid_kernels.hpp"
+#include "refine_repeats.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <set>
 #include <stdexcept>
 #include <chrono>
 #include <unordered_set>
@@ -27,7 +29,7 @@ namespace pbccs {
 const char* const kKernelNames[kKernelKinds] = {"k_fill",       "k_suffix",      "k_enumerate", "k_score",
                                                  "k_reduce",     "k_qv",          "k_best_subset", "k_compact",
                                                  "k_fill_tall",  "k_qfill_grp",   "k_qfill_coop", "k_qfill",
-                                                 "k_qscore_mid", "k_qscore_multi"};
+                                                 "k_qscore_mid", "k_qscore_multi", "k_score_wide"};
 
 namespace {
 
@@ -1993,6 +1995,235 @@ bool ArrowBatch::ApplyMutations(int zi, const std::vector<Mutation>& muts)
         if (reads_[r].status != kFillOk) reads_[r].active = false;   // AlphaBetaMismatchException -> inactive
     descDirty_ = true;
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mutations of any width: the reference's Arrow scorer refuses them
+// (MutationScorer.cpp:181-183); the rules here are its own dispatch over the wide template view.
+// ------------------------------------------------------------------------------------------------
+bool ArrowBatch::WideColumnsFit(int zi, const std::vector<MutationEx>& muts, std::string* why) const
+{
+    const HZmw& z = zmws_.at(zi);
+    auto no = [&](const char* w) {
+        if (why) *why = w;
+        return false;
+    };
+    for (const MutationEx& m : muts) {
+        if (!m.Valid() || m.start < 0 || m.end > (int)z.tpl.size()) return no("mutation invalid or outside the template");
+        if ((int)m.bases.size() > kWideMaxBases) return no("more than 7 new bases");
+        if (!is_acgt(m.bases)) return no("new bases must be A, C, G or T");
+        for (int k = 0; k < z.nReads; ++k) {
+            const HRead& h = reads_[z.readBegin + k];
+            if (!h.active) continue;
+            const OrientedEx o = orient_mutation_ex(m, h.strand, h.ts, h.te);
+            if (!o.scores) continue;
+            const int c = wide_columns_needed(o, h.te - h.ts);
+            if (c < 0) return no("mutation leaves a read's window empty");
+            if (c > kWideExtColumns) return no("mutation needs more than 8 extension columns on some read");
+        }
+    }
+    return true;
+}
+
+bool ArrowBatch::HasCheckpointedReads(int zi) const
+{
+    const HZmw& z = zmws_.at(zi);
+    for (int k = 0; k < z.nReads; ++k)
+        if (reads_[z.readBegin + k].active && reads_[z.readBegin + k].ckpt != 0) return true;
+    return false;
+}
+
+void ArrowBatch::ScoreWide(const std::vector<int>& zl, const std::vector<std::vector<MutationEx>>& muts, double fastThr,
+                           std::vector<std::vector<double>>* scores, std::vector<std::vector<double>>* perRead)
+{
+    const StreamScope bound(stream_);
+    UploadDescriptors();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    // the task list: per ZMW, per mutation, the active reads that score it, in read order
+    std::vector<WideTask> tasks;
+    for (size_t a = 0; a < zl.size(); ++a) {
+        const HZmw& z = zmws_.at(zl[a]);
+        for (const MutationEx& m : muts[a])
+            for (int k = 0; k < z.nReads; ++k) {
+                const HRead& h = reads_[z.readBegin + k];
+                if (!h.active) continue;
+                if (h.ckpt != 0) throw std::invalid_argument("a read keeps checkpointed bands: wide mutations are not scored on it");
+                const OrientedEx o = orient_mutation_ex(m, h.strand, h.ts, h.te);
+                if (!o.scores) continue;
+                WideTask t;
+                t.r = z.readBegin + k;
+                t.type = o.type;
+                t.os = o.os;
+                t.oe = o.oe;
+                t.nb = (int)o.bases.size();
+                t.slot = (int)tasks.size();
+                t.bases = 0;
+                for (size_t q = 0; q < o.bases.size() && q < 8; ++q)
+                    t.bases |= (unsigned long long)(unsigned char)o.bases[q] << (8 * q);
+                tasks.push_back(t);
+            }
+    }
+    std::vector<double> d;
+    if (!tasks.empty()) {
+        // the device list: k_score_wide's tasks first, then k_score_wide_refill's (slots keep the order above)
+        std::vector<WideTask> dev(tasks);
+        const auto refills = [&](const WideTask& t) {
+            return wide_task_refills(t.os, t.oe, t.nb, reads_[t.r].te - reads_[t.r].ts);
+        };
+        const int nExt = (int)(std::stable_partition(dev.begin(), dev.end(), [&](const WideTask& t) { return !refills(t); }) -
+                               dev.begin());
+        const int nRefill = (int)dev.size() - nExt;
+        upload(dWide_, dev, stream_);
+        dWideDelta_.reserve(tasks.size(), false);
+        const DevBatch B = View();
+        if (nExt > 0) Timed(kKScoreWide, [&] { launch_score_wide(B, dWide_.ptr, nExt, dWideDelta_.ptr, stream_); });
+        PBCCS_HIP(hipGetLastError());
+        for (int attempt = 0; nRefill > 0; ++attempt) {   // the bump scratch's grow-and-rerun protocol (RunRound)
+            PBCCS_HIP(hipMemsetAsync(dScratchTop_.ptr, 0, sizeof(unsigned long long), stream_));
+            PBCCS_HIP(hipMemsetAsync(dScratchOverflow_.ptr, 0, sizeof(int), stream_));
+            ScoreScratch sc;
+            sc.pool = dScratch_.ptr;
+            sc.top = dScratchTop_.ptr;
+            sc.cap = dScratch_.cap;
+            sc.overflow = dScratchOverflow_.ptr;
+            Timed(kKScoreWide, [&] {
+                launch_score_wide_refill(B, dWide_.ptr + nExt, nRefill, dWideDelta_.ptr, sc, wideRows_, stream_);
+            });
+            PBCCS_HIP(hipGetLastError());
+            int ovf = 0;
+            d2h(&ovf, dScratchOverflow_.ptr, sizeof(int), stream_);
+            PBCCS_HIP(hipStreamSynchronize(stream_));
+            if (!ovf) break;
+            if (attempt > 12) throw DeviceError("scratch overflow");
+            if (ovf & 4) wideRows_ = std::min(wideRows_ * 4, 1 << 24);   // a refill's band outgrew its share (capped at I + 1 rows in the kernel)
+            if (ovf & 1) dScratch_.reserve(dScratch_.cap * 4, false);
+        }
+        if (profiling_) stats_[kKScoreWide].cells += (double)tasks.size();
+        download(d, dWideDelta_, tasks.size(), stream_);
+        PBCCS_HIP(hipStreamSynchronize(stream_));
+        counters_.scoreLaunches += 1;
+        counters_.scoreTasks += (long long)tasks.size();
+    }
+    // the ordered reduction with the fast-score break (MultiReadMutationScorer.cpp:352-362), as k_reduce sums
+    scores->assign(zl.size(), {});
+    if (perRead) perRead->assign(zl.size(), {});
+    size_t t = 0;
+    for (size_t a = 0; a < zl.size(); ++a) {
+        const HZmw& z = zmws_[zl[a]];
+        (*scores)[a].assign(muts[a].size(), 0.0);
+        if (perRead) (*perRead)[a].assign(muts[a].size() * (size_t)z.nReads, nan);
+        for (size_t m = 0; m < muts[a].size(); ++m) {
+            double sum = 0.0;
+            bool broke = false;
+            for (int k = 0; k < z.nReads; ++k) {
+                const bool mine = t < tasks.size() && tasks[t].r == z.readBegin + k;
+                // (tasks are in (mutation, read) order, one per scoring read: the next task is this read's or a later one's)
+                const HRead& h = reads_[z.readBegin + k];
+                const bool scoresIt = h.active && orient_mutation_ex(muts[a][m], h.strand, h.ts, h.te).scores;
+                if (scoresIt) {
+                    if (!mine) throw DeviceError("wide task list out of step");
+                    if (perRead) (*perRead)[a][m * (size_t)z.nReads + k] = d[t];
+                    if (!broke) sum += d[t];
+                    ++t;
+                }
+                if (sum < fastThr) broke = true;
+            }
+            (*scores)[a][m] = sum;
+        }
+        counters_.mutations += (long long)muts[a].size();
+    }
+}
+
+bool ArrowBatch::ApplyMutationsEx(int zi, const std::vector<MutationEx>& muts)
+{
+    const StreamScope bound(stream_);
+    HZmw& z = zmws_.at(zi);
+    // an insertion at (or past) the template's end throws in the reference (apply_mutations)
+    for (const MutationEx& m : muts)
+        if (m.type == 0 && m.start >= (int)z.tpl.size()) return false;
+    // overlapping edits have no target-to-query map (apply_mutations_ex catches only those whose transcript grows)
+    {
+        std::vector<MutationEx> sorted(muts);
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t k = 1; k < sorted.size(); ++k)
+            if (sorted[k].start < sorted[k - 1].end) return false;
+    }
+    std::string next;
+    std::vector<int> mtp;
+    if (!apply_mutations_ex(z.tpl, muts, &next, &mtp) || next.empty() || !is_acgt(next)) return false;
+    z.tpl = next;
+    UploadTemplate(zi);
+    std::vector<int> refill;
+    for (int k = 0; k < z.nReads; ++k) {
+        HRead& r = reads_[z.readBegin + k];
+        r.ts = mtp[r.ts];
+        r.te = mtp[r.te];
+        if (r.active) refill.push_back(z.readBegin + k);
+    }
+    descDirty_ = true;
+    FillReads(refill);
+    for (int r : refill)
+        if (reads_[r].status != kFillOk) reads_[r].active = false;   // AlphaBetaMismatchException -> inactive
+    descDirty_ = true;
+    return true;
+}
+
+// RefineRepeats for the Arrow scorer: refine_repeats_lockstep (refine_repeats.hpp, shared with QuiverBatch) over
+// k_score_wide and this batch's refill.  FastIsFavorable is Score(m, FastScoreThreshold) > 0.04 on the double sum.
+void ArrowBatch::RefineRepeats(const std::vector<int>& zl, int repeatLength, int minRepeatElements,
+                               const RefineOptions& ro, std::vector<long long>* nTested,
+                               std::vector<long long>* nApplied, std::vector<char>* converged,
+                               std::vector<int>* status)
+{
+    const StreamScope bound(stream_);
+    struct Ops {
+        ArrowBatch& B;
+        const std::string& Template(int z) { return B.zmws_[z].tpl; }
+        int Refuse(int z, const std::vector<MutationEx>& cand)
+        {
+            if (B.HasCheckpointedReads(z)) return 3;
+            return B.WideColumnsFit(z, cand) ? 0 : 2;   // the 8-column rule
+        }
+        void Score(const std::vector<int>& act, const std::vector<std::vector<MutationEx>>& cand,
+                   std::vector<std::vector<float>>* score, std::vector<std::vector<char>>* favourable)
+        {
+            // one threshold per launch: the first ZMW's, as Refine
+            const double fastThr = B.zmws_[act[0]].opt.fastScoreThreshold;
+            std::vector<std::vector<double>> sc;
+            B.ScoreWide(act, cand, fastThr, &sc);
+            score->assign(act.size(), {});
+            favourable->assign(act.size(), {});
+            for (size_t a = 0; a < act.size(); ++a)
+                for (double v : sc[a]) {
+                    (*score)[a].push_back((float)v);
+                    (*favourable)[a].push_back(v > kMinFavorableScoreDiff ? 1 : 0);
+                }
+        }
+        void Edit(int z, const std::string& next, const std::vector<int>& mtp, std::vector<int>* refill)
+        {
+            HZmw& hz = B.zmws_[z];
+            hz.tpl = next;
+            B.UploadTemplate(z);
+            for (int q = 0; q < hz.nReads; ++q) {
+                HRead& h = B.reads_[hz.readBegin + q];
+                h.ts = mtp[h.ts];
+                h.te = mtp[h.te];
+                if (h.active) {
+                    B.EnsureCapacity(hz.readBegin + q);
+                    refill->push_back(hz.readBegin + q);
+                }
+            }
+            B.descDirty_ = true;
+        }
+        void Refill(const std::vector<int>& reads)
+        {
+            B.FillReads(reads);
+            for (int r : reads)
+                if (B.reads_[r].status != kFillOk) B.reads_[r].active = false;   // AlphaBetaMismatchException -> inactive
+            B.descDirty_ = true;
+        }
+    } ops{*this};
+    refine_repeats_lockstep(ops, zl, repeatLength, minRepeatElements, ro, nTested, nApplied, converged, status);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -265,9 +265,10 @@ void ckpt_policy(int* K, int* minLen);
 // within one workspace slot
 // The Quiver family's kinds (kKQ*) are the QuiverBatch fills (four reads per wavefront, a wave per read on the side
 // stream, the lane-serial fill) its batched middle-case scoring and the repeat rounds' multi-base scoring (cells = tasks).
+// kKScoreWide: Arrow's scoring of mutations of any width (k_score_wide and k_score_wide_refill; cells = tasks).
 enum KernelKind {
     kKFill = 0, kKSuffix, kKEnumerate, kKScore, kKReduce, kKQv, kKSelect, kKCompact, kKFillTall,
-    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKernelKinds
+    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKScoreWide, kKernelKinds
 };
 extern const char* const kKernelNames[kKernelKinds];
 
@@ -393,6 +394,27 @@ public:
     void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs);
     // ApplyMutations (MultiReadMutationScorer.cpp:235-267).  Returns false on an invalid edit.
     bool ApplyMutations(int z, const std::vector<Mutation>& muts);
+    // ---- mutations of any width (k_score_wide) -------------------------------------------
+    // The 8-column rule: no active read that scores one of the mutations needs more than kWideExtColumns
+    // extension columns for it, every mutation is valid, inside the template, of at most kWideMaxBases ACGT bases.
+    // Host only; `why` (may be NULL) receives the reason of a refusal.
+    bool WideColumnsFit(int z, const std::vector<MutationEx>& muts, std::string* why = nullptr) const;
+    // A read of the ZMW keeps checkpointed bands: k_score_wide cannot score it
+    bool HasCheckpointedReads(int z) const;
+    // Score(m, fastThr) of every listed mutation (one list per ZMW; the caller has checked WideColumnsFit and
+    // HasCheckpointedReads): the read-ordered sum with the fast-score break (MultiReadMutationScorer.cpp:338-368).
+    // perRead (optional): [m * nReads + k] the delta of read k, NaN where the read does not score the mutation.
+    void ScoreWide(const std::vector<int>& zmws, const std::vector<std::vector<MutationEx>>& muts, double fastThr,
+                   std::vector<std::vector<double>>* scores, std::vector<std::vector<double>>* perRead = nullptr);
+    // ApplyMutations for any width: the template edit, windows through TargetToQueryPositions, refill.
+    bool ApplyMutationsEx(int z, const std::vector<MutationEx>& muts);
+    // AbstractRefineConsensus (Consensus-inl.hpp:159-251) over RepeatMutationEnumerator for the listed ZMWs in
+    // lock-step rounds: one k_score_wide launch and one refill per round.  The favourable test is
+    // Score(m, FastScoreThreshold) > 0.04.  status[k]: 0 ok, 1 an edit could not be applied, 2 a candidate broke
+    // the 8-column rule (nothing of that ZMW is scored in that round, its loop ends), 3 a read with checkpointed bands.
+    void RefineRepeats(const std::vector<int>& zmws, int repeatLength, int minRepeatElements, const RefineOptions& ro,
+                       std::vector<long long>* nTested, std::vector<long long>* nApplied, std::vector<char>* converged,
+                       std::vector<int>* status);
     // Diploid site calling (Arrow/Diploid.cpp).  The site tensor of template positions
     // [begin, end): [site][read][9] floats, Scores(m, 0) of Substitution / Insertion(p, ACGT) and Deletion(p)
     // rounded to float, left on the device (valid until the next scoring call); SiteScores downloads it.
@@ -566,6 +588,9 @@ private:
     DevVec<unsigned long long>& dStats_;
     DevVec<long long> dTrace_;   // PBCCS_FILL_TRACE diagnostics
     DevVec<float> dSite_;        // the site tensor (SiteScoresDevice)
+    DevVec<WideTask> dWide_;     // the task list of k_score_wide and k_score_wide_refill and its deltas (ScoreWide)
+    DevVec<double> dWideDelta_;
+    int wideRows_ = 64;          // band values per column a refill of k_score_wide_refill may take (grown on overflow)
     DiploidScratch diploid_;
     struct Pending {
         int kind;

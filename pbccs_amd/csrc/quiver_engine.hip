@@ -1,5 +1,6 @@
 // pbccs_amd/csrc/quiver_engine.hip -- QuiverBatch (quiver_engine.hpp).
 #include "quiver_engine.hpp"
+#include "refine_repeats.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -877,29 +878,6 @@ int columns_needed(int type, int os, int oe, int nb, int J)
     return newLen + 1;
 }
 
-struct ScoredEx {
-    int idx, pos;
-    float score;
-};
-
-std::vector<ScoredEx> best_subset_ex(std::vector<ScoredEx> in, int sep)   // Consensus-inl.hpp:98-118
-{
-    if (sep == 0) return in;
-    std::vector<ScoredEx> out;
-    while (!in.empty()) {
-        size_t best = 0;
-        for (size_t k = 1; k < in.size(); ++k)
-            if (in[best].score < in[k].score) best = k;
-        const ScoredEx b = in[best];
-        out.push_back(b);
-        std::vector<ScoredEx> keep;
-        for (const ScoredEx& s : in)
-            if (!(b.pos - sep <= s.pos && s.pos <= b.pos + sep)) keep.push_back(s);
-        in.swap(keep);
-    }
-    return out;
-}
-
 }  // namespace
 
 bool QuiverBatch::ColumnsFit(int zi, const std::vector<MutationEx>& muts) const
@@ -1465,96 +1443,50 @@ void QuiverBatch::ScoreRoundEx(const std::vector<int>& zs, const std::vector<std
     QHIP(hipStreamSynchronize(stream_));
 }
 
-// AbstractRefineConsensus (Consensus-inl.hpp:159-251) over RepeatMutationEnumerator, scorers in lock-step
+// AbstractRefineConsensus (Consensus-inl.hpp:159-251) over RepeatMutationEnumerator, scorers in lock-step: the
+// loop is refine_repeats_lockstep (refine_repeats.hpp, shared with ArrowBatch), over this batch's scoring and refill
 void QuiverBatch::RefineRepeatsMany(const std::vector<int>& zs, int repeatLength, int minRepeatElements,
                                     const RefineOptions& ro, std::vector<long long>* nTested,
                                     std::vector<long long>* nApplied, std::vector<char>* converged,
                                     std::vector<int>* status)
 {
-    const int n = (int)zs.size();
-    nTested->assign(n, 0);
-    nApplied->assign(n, 0);
-    converged->assign(n, 0);
-    status->assign(n, 0);
-    std::vector<char> done(n, 0);
-    std::vector<int> iter(n, 0);
-    std::vector<std::set<std::string>> history(n);
-    std::vector<std::vector<int>> centers(n);
-    if (ro.maxIterations <= 0) return;
-    for (;;) {
-        std::vector<int> act, idx;
-        std::vector<std::vector<MutationEx>> cand;
-        for (int k = 0; k < n; ++k) {
-            if (done[k]) continue;
-            const std::string& tpl = zmws_[zs[k]].tpl;
-            std::vector<MutationEx> c;
-            if (iter[k] == 0) repeat_mutations(tpl, repeatLength, minRepeatElements, 0, (int)tpl.size(), &c);
-            else nearby_repeat_mutations(tpl, repeatLength, minRepeatElements, centers[k], ro.mutationNeighborhood, &c);
-            if (!ColumnsFit(zs[k], c)) {   // the 8-column rule: nothing of this scorer is scored
-                (*status)[k] = 2;
-                done[k] = 1;
-                continue;
-            }
-            (*nTested)[k] += (long long)c.size();
-            act.push_back(zs[k]);
-            idx.push_back(k);
-            cand.push_back(std::move(c));
-        }
-        if (act.empty()) break;
-        std::vector<long long> mutStart;
-        std::vector<double> score;
-        std::vector<unsigned char> favFlag;
-        ScoreRoundEx(act, cand, &mutStart, &score, &favFlag);
-        std::vector<int> refill;
-        for (size_t a = 0; a < act.size(); ++a) {
-            const int k = idx[a];
-            HZmw& z = zmws_[act[a]];
-            std::vector<ScoredEx> fav;
-            for (int m = 0; m < (int)cand[a].size(); ++m)
-                if (favFlag[(size_t)(mutStart[a] + m)])
-                    fav.push_back({m, cand[a][m].start, (float)score[(size_t)(mutStart[a] + m)]});
-            if (fav.empty()) {
-                (*converged)[k] = 1;
-                done[k] = 1;
-                continue;
-            }
-            std::vector<ScoredEx> best = best_subset_ex(fav, ro.mutationSeparation);
-            std::vector<MutationEx> muts;
-            for (const ScoredEx& s : best) muts.push_back(cand[a][s.idx]);
-            if (best.size() > 1) {
-                std::string nx;
-                std::vector<int> mtp;
-                if (apply_mutations_ex(z.tpl, muts, &nx, &mtp) && history[k].count(nx)) {
-                    best.resize(1);
-                    muts.resize(1);
+    struct Ops {
+        QuiverBatch& B;
+        const std::string& Template(int z) { return B.zmws_[z].tpl; }
+        int Refuse(int z, const std::vector<MutationEx>& cand) { return B.ColumnsFit(z, cand) ? 0 : 2; }   // the 8-column rule
+        void Score(const std::vector<int>& act, const std::vector<std::vector<MutationEx>>& cand,
+                   std::vector<std::vector<float>>* score, std::vector<std::vector<char>>* favourable)
+        {
+            std::vector<long long> mutStart;
+            std::vector<double> sc;
+            std::vector<unsigned char> favFlag;
+            B.ScoreRoundEx(act, cand, &mutStart, &sc, &favFlag);
+            score->assign(act.size(), {});
+            favourable->assign(act.size(), {});
+            for (size_t a = 0; a < act.size(); ++a)
+                for (size_t m = 0; m < cand[a].size(); ++m) {
+                    (*score)[a].push_back((float)sc[(size_t)mutStart[a] + m]);
+                    (*favourable)[a].push_back(favFlag[(size_t)mutStart[a] + m] ? 1 : 0);
                 }
-            }
-            (*nApplied)[k] += (long long)best.size();
-            history[k].insert(z.tpl);
-            centers[k].clear();
-            for (const ScoredEx& s : fav) centers[k].push_back(s.pos);
-            std::string next;
-            std::vector<int> mtp;
-            if (!apply_mutations_ex(z.tpl, muts, &next, &mtp) || next.empty()) {
-                (*status)[k] = 1;
-                done[k] = 1;
-                continue;
-            }
-            z.tpl = next;
-            for (int r : z.reads) {
-                HRead& h = reads_[r];
+        }
+        void Edit(int z, const std::string& next, const std::vector<int>& mtp, std::vector<int>* refill)
+        {
+            HZmw& hz = B.zmws_[z];
+            hz.tpl = next;
+            for (int r : hz.reads) {
+                HRead& h = B.reads_[r];
                 h.ts = mtp[h.ts];
                 h.te = mtp[h.te];
                 if (h.active) {
-                    EnsureCapacity(r);
-                    refill.push_back(r);
+                    B.EnsureCapacity(r);
+                    refill->push_back(r);
                 }
             }
-            dirty_ = true;
-            if (++iter[k] >= ro.maxIterations) done[k] = 1;
+            B.dirty_ = true;
         }
-        if (!refill.empty()) Fill(refill);   // a refill that mismatches marks the read inactive
-    }
+        void Refill(const std::vector<int>& reads) { B.Fill(reads); }
+    } ops{*this};
+    refine_repeats_lockstep(ops, zs, repeatLength, minRepeatElements, ro, nTested, nApplied, converged, status);
 }
 
 std::vector<std::vector<int>> QuiverBatch::QVsMany(const std::vector<int>& zs)   // ConsensusQVs (:274-295)

@@ -81,7 +81,7 @@ class CCounters(ctypes.Structure):
                 ("create_upload_ns", ctypes.c_longlong), ("derive_ns", ctypes.c_longlong),
                 ("fill_work", ctypes.c_longlong * 16), ("scan_reads", ctypes.c_longlong),
                 ("uncertain_reads", ctypes.c_longlong), ("exact_rounds", ctypes.c_longlong),
-                ("uncertain_why", ctypes.c_longlong * 4)]
+                ("uncertain_why", ctypes.c_longlong * 4), ("repeat_skipped_ckpt", ctypes.c_longlong)]
 
 
 class CQvModelParams(ctypes.Structure):
@@ -353,6 +353,15 @@ SIGNATURES = {
     "pbccs_quiver_polish_batch_ex": (I, [P, ctypes.POINTER(CQuiverConfig), ctypes.POINTER(ctypes.c_char_p), I,
                                          ctypes.POINTER(CQuiverZmw), I, ctypes.POINTER(CRefineOptions),
                                          ctypes.POINTER(CRepeatOptions), PLL, PLL, ctypes.POINTER(CQuiverResult)]),
+    # Arrow: mutations of any width and repeat refinement
+    "pbccs_scorer_score_many_ex": (I, [P, PMX, I, D, PD]),
+    "pbccs_scorer_scores_ex": (I, [P, PMX, D, PD]),
+    "pbccs_scorer_is_favorable_ex": (I, [P, PMX, I, PI]),
+    "pbccs_scorer_apply_mutations_ex": (I, [P, PMX, I]),
+    "pbccs_refine_repeats": (I, [P, ctypes.POINTER(CRepeatOptions), PLL, PLL, PI]),
+    "pbccs_wide_columns_needed": (I, [PMX, I, I, I, PI]),
+    "pbccs_polish_batch_ex": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
+                                  ctypes.POINTER(CRepeatOptions), PLL, PLL, ctypes.POINTER(CZmwOutput)]),
     # Diploid site calling
     "pbccs_is_site_heterozygous": (I, [PF, I, I, ctypes.c_float, PI, ctypes.POINTER(CDiploidSite), PI]),
     "pbccs_scorer_site_scores": (I, [P, I, I, PF, ctypes.c_longlong, PLL]),

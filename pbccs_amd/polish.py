@@ -146,13 +146,40 @@ def polish_many(batches):
     L.check(batches[0]._lib.pbccs_batch_polish_many(hs, n, outs))
 
 
-def polish_zmws(zmws, settings=None, engine=None):
+def _polish_repeats(zmws, settings, engine, repeats, one_batch):
+    """pbccs_polish_batch_ex: RefineConsensus, RefineRepeats(repeat_length, min_repeat_elements), ConsensusQVs per
+    ZMW; the records gain n_repeat_tested / n_repeat_applied."""
+    from . import default_engine
+    engine = engine or default_engine()
+    settings = settings or ConsensusSettings()
+    repeat_length, min_repeat_elements = repeats
+    m = _Marshalled(zmws)
+    n = len(zmws)
+    opts = settings._c()
+    if one_batch and opts.zmws_per_batch <= 0:
+        opts.zmws_per_batch = max(1, n)   # polish_zmws: one device batch
+    ro = L.CRepeatOptions(int(repeat_length), int(min_repeat_elements), 1, 10, 20)
+    rt = (ctypes.c_longlong * max(1, n))()
+    ra = (ctypes.c_longlong * max(1, n))()
+    L.check(L.load().pbccs_polish_batch_ex(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(ro), rt, ra, m._outs))
+    res = m.results()
+    for i, r in enumerate(res):
+        r["n_repeat_tested"] = rt[i]
+        r["n_repeat_applied"] = ra[i]
+    return res
+
+
+def polish_zmws(zmws, settings=None, engine=None, repeats=None):
     """Polish ZMWs on the GPU (upload, hot path, download).
 
     zmws: list of dicts {draft, snr (4), reads: [{seq, strand, ts, te, full_pass?}]}.
     Returns one dict per ZMW: status, consensus, qvs, add_read_results, zscores, zg, za, predicted_accuracy,
     n_tested, n_applied, n_passes, status_counts.
+    repeats=(repeat_length, min_repeat_elements): RefineRepeats between RefineConsensus and ConsensusQVs
+    (pbccs_polish_batch_ex); the records then also hold n_repeat_tested and n_repeat_applied.
     """
+    if repeats is not None:
+        return _polish_repeats(zmws, settings, engine, repeats, True)
     b = PreparedBatch(zmws, settings, engine)
     try:
         b.polish()
@@ -288,10 +315,12 @@ def plan_batches(zmws, budget_bytes, max_per_batch=2000, max_len_ratio=1.5):
     return [list(order[start[b]:start[b + 1]]) for b in range(nb.value)], list(est[:n])
 
 
-def polish_stream(zmws, settings=None, engine=None):
+def polish_stream(zmws, settings=None, engine=None, repeats=None):
     """Polish a stream of heterogeneous ZMWs (pbccs_polish_batch): bucketed by length and pass count into
     memory-sized device batches that the engine's workspace slots pull largest-first from one queue, like
-    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws()."""
+    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws(); `repeats` as there."""
+    if repeats is not None:
+        return _polish_repeats(zmws, settings, engine, repeats, False)
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
