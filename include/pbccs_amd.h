@@ -1034,6 +1034,62 @@ typedef struct {
 } pbccs_window_stats;
 int pbccs_window_stats_get(pbccs_engine* eng, pbccs_window_stats* out, int reset);
 
+/* ---- per-base rich QVs --------------------------------------------------------------
+ * ConsensusQVs folds the scores of a position's unique single-base mutations into one QV.  The rich QVs are the
+ * same sum taken apart by mutation type: sub_qv / ins_qv / del_qv = ProbabilityToQV(1 - 1 / (1 + S)) with S the
+ * sum of e^score over the position's substitutions / insertions / deletion with a score below 0, in enumeration
+ * order (raw and unclipped, as qvs; an empty sum gives the value it gives there), and sub_tag / ins_tag = the base
+ * of the best-scoring substitution / insertion (scores >= 0 included, the first in enumeration order on a tie;
+ * 'N' only where none was enumerated).  The qvs returned beside them are pbccs_consensus_qvs', bit for bit.
+ * Names follow the mutation type; file formats name by error type, the inverse: PacBio's DeletionQV / DeletionTag
+ * (dq / dt: a base is missing before this one) are ins_qv / ins_tag, InsertionQV (iq: this base is spurious) is
+ * del_qv, sq / st are sub_qv / sub_tag.
+ * All five are caller buffers of cap entries (the tags are not NUL-terminated); len = the entries written, 0 for a
+ * ZMW that ends neither SUCCESS nor POOR_QUALITY, -required when cap is too small (nothing is written then). */
+typedef struct {
+    int* sub_qv;
+    int* ins_qv;
+    int* del_qv;
+    char* sub_tag;
+    char* ins_tag;
+    int cap;
+    int len;
+} pbccs_rich_qvs;
+
+/* pbccs_consensus_qvs / pbccs_quiver_consensus_qvs with the rich QVs: the same sweep, then k_qv_rich / k_qqv_rich.
+ * qvs has rich->cap entries; *n = the template length; PBCCS_ERANGE (and rich->len = -required) when cap is
+ * smaller. */
+int pbccs_consensus_qvs_rich(pbccs_scorer* s, int* qvs, pbccs_rich_qvs* rich, int* n);
+int pbccs_quiver_consensus_qvs_rich(pbccs_quiver_scorer* s, int* qvs, pbccs_rich_qvs* rich, int* n);
+
+/* What the batched calls take beyond their first form, one struct per family of calls; every member may be NULL,
+ * and with all of them NULL each call is exactly the call it extends. */
+typedef struct {
+    const pbccs_repeat_options* repeats;   /* pbccs_polish_batch_ex's (not used by the windowed calls) */
+    long long* repeat_tested;              /* n entries */
+    long long* repeat_applied;
+    pbccs_rich_qvs* rich;                  /* n entries, one per ZMW */
+} pbccs_polish_extras;
+
+/* pbccs_polish_batch_ex with extras. */
+int pbccs_polish_batch_ex2(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                           const pbccs_polish_extras* extras, pbccs_zmw_output* out);
+/* pbccs_quiver_polish_batch_ex with extras. */
+int pbccs_quiver_polish_batch_ex2(pbccs_engine* eng, const pbccs_quiver_config* configs,
+                                  const char* const* chemistries, int n_configs, const pbccs_quiver_zmw* zmws, int n,
+                                  const pbccs_refine_options* opts, const pbccs_polish_extras* extras,
+                                  pbccs_quiver_result* out);
+/* pbccs_polish_windowed with extras: the stitched rich arrays are the pieces [cut_begin, cut_end) of the windows'
+ * arrays, as the stitched qvs are; a fallback ZMW gets its whole-draft route's. */
+int pbccs_polish_windowed_ex(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                             const pbccs_window_options* w, const pbccs_polish_extras* extras, pbccs_zmw_output* out,
+                             pbccs_window_info* info);
+/* pbccs_ccs_batch_ex3 with extras. */
+int pbccs_ccs_batch_ex4(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_window_options* win,
+                        const pbccs_polish_options* opts, const pbccs_polish_extras* extras, pbccs_ccs_output* out,
+                        pbccs_window_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -455,4 +455,56 @@ inline std::vector<int> ConsensusQVs(Arrow::ArrowMultiReadMutationScorer& mms)
     return q;
 }
 
+// Per-base rich QVs (no reference twin): ConsensusQVs' sum of a position taken apart by mutation
+// type.  Qvs is ConsensusQVs(mms); SubQv / InsQv / DelQv are the QVs of the partial sums over the position's
+// substitutions / insertions / deletion; Tags = (SubTag, InsTag), the base of its best-scoring substitution /
+// insertion.  Names follow the mutation type; file formats name by error type, the inverse: PacBio's DeletionQV /
+// DeletionTag (dq / dt) are InsQv / InsTag, InsertionQV (iq) is DelQv, sq / st are SubQv / SubTag.
+struct RichConsensusQVs {
+    std::vector<int> Qvs, SubQv, InsQv, DelQv;
+    std::pair<std::string, std::string> Tags;   // (SubTag, InsTag)
+    const std::string& SubTag() const { return Tags.first; }
+    const std::string& InsTag() const { return Tags.second; }
+};
+
+namespace detail {
+// shared by the Arrow and the Quiver overloads: call(qvs, rich, n) is the family's pbccs_*_consensus_qvs_rich
+template <typename Call>
+inline RichConsensusQVs RichQVs(int length, Call call)
+{
+    const size_t cap = (size_t)(length > 0 ? length : 1);
+    RichConsensusQVs r;
+    r.Qvs.resize(cap);
+    r.SubQv.resize(cap);
+    r.InsQv.resize(cap);
+    r.DelQv.resize(cap);
+    r.Tags.first.resize(cap);
+    r.Tags.second.resize(cap);
+    pbccs_rich_qvs c;
+    c.sub_qv = r.SubQv.data();
+    c.ins_qv = r.InsQv.data();
+    c.del_qv = r.DelQv.data();
+    c.sub_tag = &r.Tags.first[0];
+    c.ins_tag = &r.Tags.second[0];
+    c.cap = (int)cap;
+    c.len = 0;
+    int n = 0;
+    Check(call(r.Qvs.data(), &c, &n));
+    r.Qvs.resize(n);
+    r.SubQv.resize(n);
+    r.InsQv.resize(n);
+    r.DelQv.resize(n);
+    r.Tags.first.resize(n);
+    r.Tags.second.resize(n);
+    return r;
+}
+}  // namespace detail
+
+inline RichConsensusQVs ConsensusRichQVs(Arrow::ArrowMultiReadMutationScorer& mms)
+{
+    return detail::RichQVs(mms.TemplateLength(), [&](int* qvs, pbccs_rich_qvs* rich, int* n) {
+        return pbccs_consensus_qvs_rich(mms.Handle(), qvs, rich, n);
+    });
+}
+
 }  // namespace ConsensusCore

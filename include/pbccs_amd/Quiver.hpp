@@ -626,4 +626,12 @@ inline std::vector<int> ConsensusQVs(AbstractMultiReadMutationScorer& mms)
     return q;
 }
 
+// ConsensusRichQVs over a Quiver scorer (RichConsensusQVs: ConsensusCore.hpp)
+inline RichConsensusQVs ConsensusRichQVs(AbstractMultiReadMutationScorer& mms)
+{
+    return detail::RichQVs(mms.TemplateLength(), [&](int* qvs, pbccs_rich_qvs* rich, int* n) {
+        return pbccs_quiver_consensus_qvs_rich(mms.Handle(), qvs, rich, n);
+    });
+}
+
 }  // namespace ConsensusCore

@@ -130,9 +130,9 @@ class Engine:
         _lib_mod.check(load().pbccs_engine_set_profiling(self._h, 1 if on else 0))
 
     def kernel_stats(self, reset=False):
-        arr = (_lib_mod.CKernelStat * 16)()
+        arr = (_lib_mod.CKernelStat * 32)()
         n = ctypes.c_int()
-        _lib_mod.check(load().pbccs_engine_kernel_stats(self._h, arr, 16, ctypes.byref(n), 1 if reset else 0))
+        _lib_mod.check(load().pbccs_engine_kernel_stats(self._h, arr, 32, ctypes.byref(n), 1 if reset else 0))
         return {arr[i].name.decode(): {"launches": arr[i].launches, "device_ms": arr[i].device_ms,
                                        "cells": arr[i].cells, "bytes": arr[i].bytes, "wave_s": arr[i].wave_s}
                 for i in range(n.value)}
@@ -363,6 +363,7 @@ def wide_columns_needed(m, strand, template_start, template_end):
                                                     int(template_end), ctypes.byref(n)))
     return n.value
 from .diploid import DiploidSite, IsSiteHeterozygous  # noqa: E402,F401
+from .richqv import ConsensusRichQVs, rich_feature_tracks  # noqa: E402,F401
 from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
                     TargetToQueryPositions, UnsupportedFeatureError, align_band_stats, align_batch, align_stats)

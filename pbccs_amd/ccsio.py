@@ -139,11 +139,15 @@ def _f32(x):
                                                                ("inf" if x > 0 else "-inf"))
 
 
-def ccs_sam_record(movie, hole, result, snr):
+def ccs_sam_record(movie, hole, result, snr, rich=False):
     """The CCS record of src/main/ccs.cpp:105-172 as a SAM text line (unmapped, flag 4; MAPQ 255).
 
     result: one pbccs_amd polish result (status Success).  Tags in the reference's order: RG zm np rq sn pq
     za zs rs.  rq = int32(1000 * predAcc) (truncation, ccs.cpp:137); floats are the float32 casts.
+    rich=True (a result made with rich_qvs=True): the per-base rich QVs follow as dq iq sq (QVsToASCII-clipped
+    Phred+33 strings) and dt st (base strings).  The file format names by error type, the inverse of the record's
+    mutation types: dq / dt (DeletionQV / DeletionTag, a base is missing before this one) are
+    ins_qv / ins_tag, iq (InsertionQV, this base is spurious) is del_qv, sq / st are sub_qv / sub_tag.
     """
     name = f"{movie}/{hole}/ccs"
     qual = QVsToASCII(result["qvs"])
@@ -160,6 +164,9 @@ def ccs_sam_record(movie, hole, result, snr):
             f"pq:f:{_f32(result['predicted_accuracy'])}", f"za:f:{_f32(result['za'])}",
             "zs:B:f," + ",".join(_f32(z) for z in zs) if zs else "zs:B:f",
             "rs:B:i," + ",".join(str(int(c)) for c in result["status_counts"])]
+    if rich:
+        tags += [f"dq:Z:{QVsToASCII(result['ins_qv'])}", f"iq:Z:{QVsToASCII(result['del_qv'])}",
+                 f"sq:Z:{QVsToASCII(result['sub_qv'])}", f"dt:Z:{result['ins_tag']}", f"st:Z:{result['sub_tag']}"]
     fields = [name, "4", "*", "0", "255", "*", "*", "0", "0", result["consensus"] or "*", qual or "*"]
     return "\t".join(fields + tags)
 

@@ -13,6 +13,7 @@
 //   k_reduce      one lane per mutation: ordered per-read sum with the fast-score break
 //                 (MultiReadMutationScorer.cpp:338-368), favourable flag (> 0.04).
 //   k_qv          one lane per template position: ConsensusQVs (Consensus-inl.hpp:274-295).
+//   k_qv_rich     k_qv plus the substitution / insertion / deletion QVs and tags of each position.
 #include "arrow_device.hpp"
 #include "arrow_kernels.hpp"
 #include "arrow_score_device.hpp"
@@ -1353,6 +1354,63 @@ __global__ void __launch_bounds__(256) k_qv(DevBatch B, ScoreWork W, const long 
     qv[qvBase[k] + p] = (int)round(-10.0 * log10(prob));
 }
 
+// ProbabilityToQV(1 - 1 / (1 + sum)) (Consensus-inl.hpp:130-138)
+__device__ __forceinline__ int sum_to_qv(double sum)
+{
+    double prob = 1.0 - 1.0 / (1.0 + sum);
+    if (prob == 0.0) prob = 2.2250738585072014e-308;   // std::numeric_limits<double>::min()
+    return (int)round(-10.0 * log10(prob));
+}
+
+// k_qv with the per-type decomposition of its sum: qv as k_qv computes it (the same loop over
+// the same scores, never the three partial sums re-added), the QVs of the partial sums over the position's
+// substitutions, insertions and deletion, and the base of the best-scoring substitution / insertion (the first in
+// enumeration order on a tie, scores >= 0 included; 'N' when none was enumerated).
+__global__ void __launch_bounds__(256) k_qv_rich(DevBatch B, ScoreWork W, const long long* __restrict__ posBase,
+                                                 const int* __restrict__ posOff, const double* __restrict__ score,
+                                                 const long long* __restrict__ qvBase, int* __restrict__ qv,
+                                                 RichQvOut R)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= W.posStart[W.nWork]) return;
+    int lo = 0, hi = W.nWork;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (W.posStart[mid] <= g) lo = mid; else hi = mid;
+    }
+    const int k = lo;
+    const int p = (int)(g - W.posStart[k]);
+    const int* po = posOff + posBase[k];
+    const double* sc = score + W.mutBase[k];
+    const int* code = W.codes + W.mutBase[k];
+    double sum = 0.0;
+    for (int m = po[p]; m < po[p + 1]; ++m) {
+        const double s = sc[m];
+        if (s < 0.0) sum += exp(s);
+    }
+    double part[3] = {0.0, 0.0, 0.0};   // by MutType: kIns, kDel, kSub
+    double bestSub = 0.0, bestIns = 0.0;
+    int tagSub = -1, tagIns = -1;
+    for (int m = po[p]; m < po[p + 1]; ++m) {
+        const double s = sc[m];
+        const int c = code[m];
+        const int type = mut_type(c);
+        const double e = s < 0.0 ? exp(s) : 0.0;
+        part[0] += type == kIns ? e : 0.0;
+        part[1] += type == kDel ? e : 0.0;
+        part[2] += type == kSub ? e : 0.0;
+        if (type == kSub && (tagSub < 0 || s > bestSub)) { bestSub = s; tagSub = mut_base(c); }
+        if (type == kIns && (tagIns < 0 || s > bestIns)) { bestIns = s; tagIns = mut_base(c); }
+    }
+    const long long o = qvBase[k] + p;
+    qv[o] = sum_to_qv(sum);
+    R.ins[o] = sum_to_qv(part[0]);
+    R.del[o] = sum_to_qv(part[1]);
+    R.sub[o] = sum_to_qv(part[2]);
+    R.subTag[o] = tagSub < 0 ? 'N' : base_char(tagSub);
+    R.insTag[o] = tagIns < 0 ? 'N' : base_char(tagIns);
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (host side)
 // ------------------------------------------------------------------------------------------------
@@ -1428,6 +1486,14 @@ void launch_qv(const DevBatch& B, const ScoreWork& W, long long nPos, const long
     if (nPos <= 0) return;
     hipLaunchKernelGGL(k_qv, dim3((unsigned)((nPos + 255) / 256)), dim3(256), 0, s, B, W, posBase, posOff, score,
                        qvBase, qv);
+}
+
+void launch_qv_rich(const DevBatch& B, const ScoreWork& W, long long nPos, const long long* posBase, const int* posOff,
+                    const double* score, const long long* qvBase, int* qv, const RichQvOut& R, hipStream_t s)
+{
+    if (nPos <= 0) return;
+    hipLaunchKernelGGL(k_qv_rich, dim3((unsigned)((nPos + 255) / 256)), dim3(256), 0, s, B, W, posBase, posOff, score,
+                       qvBase, qv, R);
 }
 
 }  // namespace pbccs

@@ -184,5 +184,16 @@ void launch_best_subset(int nWork, const long long* selBase, const int* nSel, co
                         int sep, int ldsCap, int* rank, hipStream_t s);
 void launch_qv(const DevBatch& B, const ScoreWork& W, long long nPos, const long long* posBase, const int* posOff,
                const double* score, const long long* qvBase, int* qv, hipStream_t s);
+// Per-base rich QVs, one array each so that a wave stores contiguously; indexed like qv.
+struct RichQvOut {
+    int* sub = nullptr;
+    int* ins = nullptr;
+    int* del = nullptr;
+    char* subTag = nullptr;
+    char* insTag = nullptr;
+};
+// k_qv_rich: launch_qv's qv, bit for bit, and the per-type QVs and tags beside it.
+void launch_qv_rich(const DevBatch& B, const ScoreWork& W, long long nPos, const long long* posBase, const int* posOff,
+                    const double* score, const long long* qvBase, int* qv, const RichQvOut& R, hipStream_t s);
 
 }  // namespace pbccs

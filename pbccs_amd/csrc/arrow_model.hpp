@@ -69,6 +69,14 @@ std::string reverse_complement(const std::string& s);
 long long unique_mutation_count(const std::string& tpl);
 // UniqueSingleBaseMutationEnumerator::Mutations(b, e) (MutationEnumerator.cpp:114-145), as codes.
 void unique_mutations(const std::string& tpl, int b, int e, std::vector<int>* codes);
+// Per-base rich QVs of one template, by mutation type: the QVs of the partial sums of
+// ConsensusQVs' sum over a position's substitutions, insertions and deletion, and the base of its best-scoring
+// substitution / insertion.  (File formats name by error type: ins* is PacBio's DeletionQV / DeletionTag, del its
+// InsertionQV.)
+struct RichQVs {
+    std::vector<int> subQv, insQv, delQv;
+    std::string subTag, insTag;
+};
 // UniqueNearbyMutations (MutationEnumerator-inl.hpp:50-68): std::set<Mutation> order, as codes.
 void nearby_mutations(const std::string& tpl, const std::vector<int>& centerStarts, int nbhd,
                       std::vector<int>* codes);

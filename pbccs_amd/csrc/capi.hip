@@ -534,6 +534,41 @@ int pbccs_consensus_qvs(pbccs_scorer* s, int* qvs, int cap, int* n)
     });
 }
 
+// ---- per-base rich QVs ------------------------------------------------------------------
+// One ZMW's rich arrays into the caller's buffers; false (len = -required) when they are too small.
+static bool write_rich(pbccs_rich_qvs* r, const RichQVs& v)
+{
+    const int L = (int)v.subQv.size();
+    if (r->cap < L || (L > 0 && (!r->sub_qv || !r->ins_qv || !r->del_qv || !r->sub_tag || !r->ins_tag))) {
+        r->len = -L;
+        return false;
+    }
+    std::copy(v.subQv.begin(), v.subQv.end(), r->sub_qv);
+    std::copy(v.insQv.begin(), v.insQv.end(), r->ins_qv);
+    std::copy(v.delQv.begin(), v.delQv.end(), r->del_qv);
+    std::copy(v.subTag.begin(), v.subTag.end(), r->sub_tag);
+    std::copy(v.insTag.begin(), v.insTag.end(), r->ins_tag);
+    r->len = L;
+    return true;
+}
+
+int pbccs_consensus_qvs_rich(pbccs_scorer* s, int* qvs, pbccs_rich_qvs* rich, int* n)
+{
+    if (!s || !n || !rich) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<std::vector<int>> q;
+        std::vector<RichQVs> r;
+        s->batch->QVs({s->z}, &q, &r);
+        *n = (int)q[0].size();
+        if (!qvs || !write_rich(rich, r[0])) {
+            rich->len = -*n;
+            return fail(PBCCS_ERANGE, "buffer too small");
+        }
+        std::copy(q[0].begin(), q[0].end(), qvs);
+        return PBCCS_OK;
+    });
+}
+
 // ---- batched polish -------------------------------------------------------------------------------
 void pbccs_polish_options_default(pbccs_polish_options* o)
 {
@@ -651,8 +686,9 @@ int pbccs_batch_create(pbccs_engine* eng, const pbccs_zmw_input* in, int n, cons
 void pbccs_batch_destroy(pbccs_batch* b) { delete b; }
 
 // repTested / repApplied (b->n entries each, may be NULL): RefineRepeats' counts of a batch made with repeats
+// rich (b->n entries, may be NULL): the rich QVs of each ZMW beside its qvs (k_qv_rich instead of k_qv)
 static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTested = nullptr,
-                      long long* repApplied = nullptr)
+                      long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
 {
     if (!b || (b->n > 0 && !out)) return fail(PBCCS_EINVAL, "bad argument");
     if (b->polished) return fail(PBCCS_ESTATE, "a batch polishes once");
@@ -737,9 +773,12 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
         std::vector<long long> nt, na;
         // ConsensusQVs (Consensus.h:496-512) run inside the refine loop, in the round each ZMW converges
         std::vector<std::vector<int>> qvAll;
-        B.Refine(refineZ, ro, &conv, &nt, &na, false, reclaim ? &qvAll : nullptr);
+        std::vector<RichQVs> richAll, richQ;
+        B.Refine(refineZ, ro, &conv, &nt, &na, false, reclaim ? &qvAll : nullptr, reclaim && rich ? &richAll : nullptr);
         std::vector<int> qvZ, qvIdx;
         std::vector<std::vector<int>> qvs;
+        if (rich)
+            for (int i = 0; i < n; ++i) rich[i].len = 0;
         for (size_t k = 0; k < refineZ.size(); ++k) {
             pbccs_zmw_output& q = out[refineIdx[k]];
             q.n_tested = nt[k];
@@ -748,6 +787,7 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
                 qvZ.push_back(refineZ[k]);
                 qvIdx.push_back(refineIdx[k]);
                 if (reclaim) qvs.push_back(std::move(qvAll[k]));
+                if (reclaim && rich) richQ.push_back(std::move(richAll[k]));
             } else q.status = conv[k] < 0 ? PBCCS_ZMW_OTHER : PBCCS_ZMW_NON_CONVERGENT;
         }
         for (int i = 0; i < n; ++i) {
@@ -785,7 +825,7 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
                 b->eng->repeatSkippedCkpt += skipped;
             }
         }
-        if (!reclaim) B.QVs(qvZ, &qvs);
+        if (!reclaim) B.QVs(qvZ, &qvs, rich ? &richQ : nullptr);
         for (size_t k = 0; k < qvZ.size(); ++k) {
             pbccs_zmw_output& q = out[qvIdx[k]];
             const std::string& t = B.Template(qvZ[k]);
@@ -800,6 +840,10 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
             }
             std::memcpy(q.consensus, t.c_str(), t.size() + 1);
             q.consensus_len = (int)t.size();
+            if (rich && !write_rich(&rich[qvIdx[k]], richQ[k])) {   // as a consensus buffer that is too small
+                q.status = PBCCS_ZMW_OTHER;
+                continue;
+            }
             if (q.qvs) std::copy(qvs[k].begin(), qvs[k].end(), q.qvs);
             q.status = (acc < o.min_predicted_accuracy) ? PBCCS_ZMW_POOR_QUALITY : PBCCS_ZMW_SUCCESS;
         }
@@ -810,11 +854,11 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
 // Create, polish, account and destroy one device batch of m ZMWs on `slot`.
 static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int m, const pbccs_polish_options* o,
                        pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
-                       long long* repTested = nullptr, long long* repApplied = nullptr)
+                       long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
 {
     pbccs_batch* h = nullptr;
     int r = create_batch(eng, in, m, o, slot, &h, repeats);
-    if (r == PBCCS_OK) r = polish_one(h, out, repTested, repApplied);
+    if (r == PBCCS_OK) r = polish_one(h, out, repTested, repApplied, rich);
     if (h) {
         if (h->B) merge_engine_stats(eng, *h->B);
         pbccs_batch_destroy(h);
@@ -828,7 +872,7 @@ static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, i
 // the retry changes the schedule and nothing else.  Outputs land in out[0..n) in input order.
 static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int n, const pbccs_polish_options* o,
                         pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
-                        long long* repTested = nullptr, long long* repApplied = nullptr)
+                        long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
 {
     std::vector<std::pair<int, int>> todo{{0, n}};
     // the slot's outgrown buffers go back to the device before the rerun (nothing of the slot is queued: its batches
@@ -843,7 +887,8 @@ static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, 
         }
         const int r = polish_span(eng, slot, in + span.first, span.second - span.first, o, out + span.first, repeats,
                                   repTested ? repTested + span.first : nullptr,
-                                  repApplied ? repApplied + span.first : nullptr);
+                                  repApplied ? repApplied + span.first : nullptr,
+                                  rich ? rich + span.first : nullptr);
         if (r == PBCCS_OK) continue;
         if (r != PBCCS_EOOM || span.second - span.first < 2) return r;
         eng->Slot(slot)->val.unmap_all();
@@ -1051,7 +1096,7 @@ int pbccs_plan_batches(const pbccs_zmw_input* in, int n, double budget_bytes, in
 // pbccs_polish_batch (repeats == NULL) and pbccs_polish_batch_ex: the ZMW work queue
 static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
                              const pbccs_repeat_options* repeats, long long* repTested, long long* repApplied,
-                             pbccs_zmw_output* out)
+                             pbccs_zmw_output* out, pbccs_rich_qvs* rich = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
     if (n == 0) return PBCCS_OK;
@@ -1107,6 +1152,14 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
     auto scatter = [&](int b, int e, const std::vector<pbccs_zmw_output>& bout) {
         for (int k = 0; k < e - b; ++k) out[order[b + k]] = bout[k];
     };
+    // the rich-QV structs of a span (they point at the caller's buffers, as the outputs do)
+    auto gather_rich = [&](int b, int e, std::vector<pbccs_rich_qvs>* br) {
+        br->resize(rich ? e - b : 0);
+        for (int k = 0; rich && k < e - b; ++k) (*br)[k] = rich[order[b + k]];
+    };
+    auto scatter_rich = [&](int b, int e, const std::vector<pbccs_rich_qvs>& br) {
+        for (int k = 0; rich && k < e - b; ++k) rich[order[b + k]] = br[k];
+    };
     // RefineRepeats' counts of a span, back to input order
     auto scatter_counts = [&](int b, int e, const std::vector<long long>& rt, const std::vector<long long>& ra) {
         for (int k = 0; k < e - b; ++k) {
@@ -1122,12 +1175,14 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
         std::vector<pbccs_zmw_input> bin;
         std::vector<pbccs_zmw_output> bout;
         std::vector<long long> brt, bra;
+        std::vector<pbccs_rich_qvs> brich;
         for (;;) {
             const int b = next.fetch_add(1);
             if (b >= nb || stop.load()) return;
             int r = PBCCS_OK;
             try {
                 gather(start[b], start[b + 1], &bin, &bout);
+                gather_rich(start[b], start[b + 1], &brich);
                 if (repeats) {
                     brt.assign(start[b + 1] - start[b], 0);
                     bra.assign(start[b + 1] - start[b], 0);
@@ -1137,9 +1192,11 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
             }
             if (r == PBCCS_OK)
                 r = polish_span(eng, slot, bin.data(), start[b + 1] - start[b], &o, bout.data(), repeats,
-                                repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr);
+                                repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr,
+                                rich ? brich.data() : nullptr);
             if (r == PBCCS_OK) {
                 scatter(start[b], start[b + 1], bout);
+                scatter_rich(start[b], start[b + 1], brich);
                 if (repeats) scatter_counts(start[b], start[b + 1], brt, bra);
             } else if (r == PBCCS_EOOM) {
                 std::lock_guard<std::mutex> lk(deferMu);
@@ -1169,13 +1226,17 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
         return guarded([&] {
             std::vector<pbccs_zmw_input> bin;
             std::vector<pbccs_zmw_output> bout;
+            std::vector<pbccs_rich_qvs> brich;
             for (const std::pair<int, int>& span : deferred) {
                 gather(span.first, span.second, &bin, &bout);
+                gather_rich(span.first, span.second, &brich);
                 std::vector<long long> brt(span.second - span.first, 0), bra(span.second - span.first, 0);
                 const int r = polish_retry(eng, 0, bin.data(), span.second - span.first, &o, bout.data(), repeats,
-                                           repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr);
+                                           repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr,
+                                           rich ? brich.data() : nullptr);
                 if (r != PBCCS_OK) return r;
                 scatter(span.first, span.second, bout);
+                scatter_rich(span.first, span.second, brich);
                 if (repeats) scatter_counts(span.first, span.second, brt, bra);
             }
             return PBCCS_OK;
@@ -1198,6 +1259,17 @@ int pbccs_polish_batch_ex(pbccs_engine* eng, const pbccs_zmw_input* in, int n, c
         return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
     return polish_batch_impl(eng, in, n, opts, repeats, repeats ? repeat_tested : nullptr,
                              repeats ? repeat_applied : nullptr, out);
+}
+
+int pbccs_polish_batch_ex2(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                           const pbccs_polish_extras* extras, pbccs_zmw_output* out)
+{
+    const pbccs_polish_extras none{};
+    const pbccs_polish_extras& x = extras ? *extras : none;
+    if (x.repeats && (x.repeats->repeat_length < 1 || x.repeats->repeat_length > PBCCS_MAX_MUTATION_BASES))
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return polish_batch_impl(eng, in, n, opts, x.repeats, x.repeats ? x.repeat_tested : nullptr,
+                             x.repeats ? x.repeat_applied : nullptr, out, x.rich);
 }
 
 int pbccs_engine_set_profiling(pbccs_engine* eng, int on)
@@ -1814,6 +1886,22 @@ int pbccs_quiver_consensus_qvs(pbccs_quiver_scorer* s, int* qvs, int cap, int* n
     });
 }
 
+int pbccs_quiver_consensus_qvs_rich(pbccs_quiver_scorer* s, int* qvs, pbccs_rich_qvs* rich, int* n)
+{
+    if (!s || !n || !rich) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::vector<RichQVs> r;
+        const std::vector<std::vector<int>> q = s->batch->QVsMany({s->z}, &r);
+        *n = (int)q[0].size();
+        if (!qvs || !write_rich(rich, r[0])) {
+            rich->len = -*n;
+            return fail(PBCCS_ERANGE, "buffer too small");
+        }
+        std::copy(q[0].begin(), q[0].end(), qvs);
+        return PBCCS_OK;
+    });
+}
+
 int pbccs_qv_evaluator_moves(pbccs_engine* eng, const pbccs_qv_features* read, const char* tpl, int tpl_len,
                              const pbccs_qv_model_params* params, int pin_start, int pin_end, const int* i,
                              const int* j, int n, float* inc, float* del, float* extra, float* merge)
@@ -1877,7 +1965,8 @@ int pbccs_qv_evaluator_moves(pbccs_engine* eng, const pbccs_qv_features* read, c
 static int quiver_polish_batch_impl(pbccs_engine* eng, const pbccs_quiver_config* configs,
                                     const char* const* chemistries, int n_configs, const pbccs_quiver_zmw* zmws, int n,
                                     const pbccs_refine_options* opts, const pbccs_repeat_options* rep,
-                                    long long* repeat_tested, long long* repeat_applied, pbccs_quiver_result* out)
+                                    long long* repeat_tested, long long* repeat_applied, pbccs_quiver_result* out,
+                                    pbccs_rich_qvs* rich = nullptr)
 {
     if (!eng || !configs || n_configs < 1 || n < 0 || (n > 0 && (!zmws || !out))) return fail(PBCCS_EINVAL, "bad argument");
     for (int k = 0; k < n_configs; ++k)
@@ -1995,10 +2084,13 @@ static int quiver_polish_batch_impl(pbccs_engine* eng, const pbccs_quiver_config
         const double msRefine = lap();
         std::vector<int> wantQv;
         for (int z = 0; z < n; ++z)
-            if (out[z].qvs && ok[z]) wantQv.push_back(z);
+            if ((out[z].qvs || rich) && ok[z]) wantQv.push_back(z);
         std::vector<int> qz;
         for (int z : wantQv) qz.push_back(zs[z]);
-        const std::vector<std::vector<int>> qv = qz.empty() ? std::vector<std::vector<int>>() : qb.QVsMany(qz);
+        std::vector<RichQVs> richQ;
+        const std::vector<std::vector<int>> qv =
+            qz.empty() ? std::vector<std::vector<int>>() : qb.QVsMany(qz, rich ? &richQ : nullptr);
+        for (int z = 0; rich && z < n; ++z) rich[z].len = 0;
         if (qtrace)
             std::fprintf(stderr, "[quiver] scorers %d prepare %.1f ms addread %.1f ms refine %.1f ms qvs %.1f ms\n", n,
                          msPrep, msAdd, msRefine, lap());
@@ -2014,7 +2106,8 @@ static int quiver_polish_batch_impl(pbccs_engine* eng, const pbccs_quiver_config
         }
         for (size_t k = 0; k < wantQv.size(); ++k) {
             pbccs_quiver_result& o = out[wantQv[k]];
-            if (o.consensus_cap >= (int)qv[k].size()) std::copy(qv[k].begin(), qv[k].end(), o.qvs);
+            if (o.qvs && o.consensus_cap >= (int)qv[k].size()) std::copy(qv[k].begin(), qv[k].end(), o.qvs);
+            if (rich) write_rich(&rich[wantQv[k]], richQ[k]);
         }
         {
             std::lock_guard<std::mutex> lk(eng->statsMu);
@@ -2040,6 +2133,19 @@ int pbccs_quiver_polish_batch_ex(pbccs_engine* eng, const pbccs_quiver_config* c
         return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
     return quiver_polish_batch_impl(eng, configs, chemistries, n_configs, zmws, n, opts, repeats, repeat_tested,
                                     repeat_applied, out);
+}
+
+int pbccs_quiver_polish_batch_ex2(pbccs_engine* eng, const pbccs_quiver_config* configs,
+                                  const char* const* chemistries, int n_configs, const pbccs_quiver_zmw* zmws, int n,
+                                  const pbccs_refine_options* opts, const pbccs_polish_extras* extras,
+                                  pbccs_quiver_result* out)
+{
+    const pbccs_polish_extras none{};
+    const pbccs_polish_extras& x = extras ? *extras : none;
+    if (x.repeats && (x.repeats->repeat_length < 1 || x.repeats->repeat_length > PBCCS_MAX_MUTATION_BASES))
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    return quiver_polish_batch_impl(eng, configs, chemistries, n_configs, zmws, n, opts, x.repeats, x.repeat_tested,
+                                    x.repeat_applied, out, x.rich);
 }
 
 // ---------------------------------------------------------------- Diploid site calling
@@ -2958,10 +3064,13 @@ struct WinBuf {
     std::vector<int> lens, ts, te, arr, qvs;
     std::vector<double> zsc;
     std::vector<char> cons;
+    std::vector<int> richQv;     // a rich call: the window's sub / ins / del QVs, cons.size() entries each
+    std::vector<char> richTag;   // and its sub / ins tags
 };
 
 static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options& o,
-                                const pbccs_window_options& w, pbccs_zmw_output* out, pbccs_window_info* info)
+                                const pbccs_window_options& w, pbccs_zmw_output* out, pbccs_window_info* info,
+                                pbccs_rich_qvs* rich = nullptr)
 {
     using Clock = std::chrono::steady_clock;
     auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -2979,12 +3088,14 @@ static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, in
     std::vector<pbccs_zmw_input> pin((size_t)np);
     std::vector<pbccs_zmw_output> pout((size_t)np);
     std::vector<WinBuf> buf((size_t)np);
+    std::vector<pbccs_rich_qvs> prich(rich ? (size_t)np : 0);   // the windows' rich QVs
     long long multi = 0, windows = 0, unanchored = 0;
     for (int z = 0; z < n; ++z) {
         const int nw = (int)Z[z].wins.size(), nr = std::max(0, in[z].n_reads);
         if (nw == 1) {
             pin[first[z]] = in[z];
             pout[first[z]] = out[z];
+            if (rich) prich[first[z]] = rich[z];
             continue;
         }
         ++multi;
@@ -3025,9 +3136,17 @@ static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, in
             po.qvs = B.qvs.data();
             po.add_read_results = B.arr.data();
             po.zscores = B.zsc.data();
+            if (rich) {
+                const size_t cap = B.cons.size();
+                B.richQv.assign(3 * cap, 0);
+                B.richTag.assign(2 * cap, 0);
+                prich[first[z] + x] = pbccs_rich_qvs{B.richQv.data(), B.richQv.data() + cap, B.richQv.data() + 2 * cap,
+                                                     B.richTag.data(), B.richTag.data() + cap, (int)cap, 0};
+            }
         }
     }
-    int rc = pbccs_polish_batch(eng, pin.data(), np, &o, pout.data());
+    int rc = polish_batch_impl(eng, pin.data(), np, &o, nullptr, nullptr, nullptr, pout.data(),
+                               rich ? prich.data() : nullptr);
     if (rc != PBCCS_OK) return rc;
     const auto t2 = Clock::now();
 
@@ -3119,7 +3238,10 @@ static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, in
         }
         if (nw == 1) {
             out[z] = pout[first[z]];
+            if (rich) rich[z] = prich[first[z]];
             recs[z][0].cut_end = std::max(0, out[z].consensus_len);
+        } else if (rich) {
+            rich[z].len = 0;
         }
     }
     for (size_t q = 0; q < jref.size();) {
@@ -3196,6 +3318,27 @@ static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, in
             q.status = PBCCS_ZMW_OTHER;
             continue;
         }
+        if (rich) {   // the same pieces of the windows' rich arrays
+            pbccs_rich_qvs& rq = rich[z];
+            if (rq.cap < len || !rq.sub_qv || !rq.ins_qv || !rq.del_qv || !rq.sub_tag || !rq.ins_tag) {
+                rq.len = -(int)len;
+                q.consensus_len = 0;
+                q.status = PBCCS_ZMW_OTHER;
+                continue;
+            }
+            long long ra = 0;
+            for (int x = 0; x < nw; ++x) {
+                const pbccs_window_record& R = recs[z][x];
+                const pbccs_rich_qvs& pr = prich[first[z] + x];
+                std::copy(pr.sub_qv + R.cut_begin, pr.sub_qv + R.cut_end, rq.sub_qv + ra);
+                std::copy(pr.ins_qv + R.cut_begin, pr.ins_qv + R.cut_end, rq.ins_qv + ra);
+                std::copy(pr.del_qv + R.cut_begin, pr.del_qv + R.cut_end, rq.del_qv + ra);
+                std::copy(pr.sub_tag + R.cut_begin, pr.sub_tag + R.cut_end, rq.sub_tag + ra);
+                std::copy(pr.ins_tag + R.cut_begin, pr.ins_tag + R.cut_end, rq.ins_tag + ra);
+                ra += R.cut_end - R.cut_begin;
+            }
+            rq.len = (int)len;
+        }
         long long at = 0;
         for (int x = 0; x < nw; ++x) {
             const pbccs_window_record& R = recs[z][x];
@@ -3216,10 +3359,15 @@ static int polish_windowed_impl(pbccs_engine* eng, const pbccs_zmw_input* in, in
     if (!fz.empty()) {
         std::vector<pbccs_zmw_input> fin;
         std::vector<pbccs_zmw_output> fout;
+        std::vector<pbccs_rich_qvs> frich;
         for (int z : fz) fin.push_back(in[z]), fout.push_back(out[z]);
-        rc = pbccs_polish_batch(eng, fin.data(), (int)fz.size(), &o, fout.data());
+        for (int z : fz)
+            if (rich) frich.push_back(rich[z]);
+        rc = polish_batch_impl(eng, fin.data(), (int)fz.size(), &o, nullptr, nullptr, nullptr, fout.data(),
+                               rich ? frich.data() : nullptr);
         if (rc != PBCCS_OK) return rc;
         for (size_t q = 0; q < fz.size(); ++q) out[fz[q]] = fout[q];
+        for (size_t q = 0; rich && q < fz.size(); ++q) rich[fz[q]] = frich[q];
     }
     const auto t4 = Clock::now();
     if (info)
@@ -3258,6 +3406,20 @@ int pbccs_polish_windowed(pbccs_engine* eng, const pbccs_zmw_input* in, int n, c
     return guarded([&] { return polish_windowed_impl(eng, in, n, o, *w, out, info); });
 }
 
+int pbccs_polish_windowed_ex(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                             const pbccs_window_options* w, const pbccs_polish_extras* extras, pbccs_zmw_output* out,
+                             pbccs_window_info* info)
+{
+    if (!extras || !extras->rich) return pbccs_polish_windowed(eng, in, n, opts, w, out, info);
+    if (!window_options_ok(w)) return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    if (window_check_inputs(in, n) != PBCCS_OK) return PBCCS_EINVAL;
+    pbccs_polish_options o;
+    if (opts) o = *opts;
+    else pbccs_polish_options_default(&o);
+    return guarded([&] { return polish_windowed_impl(eng, in, n, o, *w, out, info, extras->rich); });
+}
+
 int pbccs_window_stats_get(pbccs_engine* eng, pbccs_window_stats* out, int reset)
 {
     if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
@@ -3278,6 +3440,7 @@ struct CcsChunk {
     std::vector<pbccs_zmw_input> pin;   // the ZMWs that reach the polish
     std::vector<int> pinZ;
     std::vector<pbccs_zmw_output> pout;
+    std::vector<pbccs_rich_qvs> prich;   // a rich call: the caller's rich-QV structs of the ZMWs in pin
     // per-read polish outputs by position in the polish input (FilterReads order up to the maxPoaCov stop);
     // scattered back to the caller's subread order once the chunk's polish is final
     std::vector<std::vector<int>> arr;
@@ -3419,9 +3582,11 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
 
 static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
                           bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out,
-                          const pbccs_window_options* win = nullptr, pbccs_window_info* info = nullptr)
+                          const pbccs_window_options* win = nullptr, pbccs_window_info* info = nullptr,
+                          pbccs_rich_qvs* rich = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
+    for (int z = 0; rich && z < n; ++z) rich[z].len = 0;   // ZMWs that never reach the polish
     if (win && !window_options_ok(win))
         return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
     if (win && info)
@@ -3553,7 +3718,8 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 CcsChunk& C = chunks[c];
                 if (hi <= lo) continue;
                 const double p0 = since();
-                const int rc = polish_span(eng, slot, C.pin.data() + lo, hi - lo, &o, C.pout.data() + lo);
+                const int rc = polish_span(eng, slot, C.pin.data() + lo, hi - lo, &o, C.pout.data() + lo, nullptr, nullptr,
+                                           nullptr, rich ? C.prich.data() + lo : nullptr);
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d polish slot %d zmws %d %.1f-%.1f ms\n", c, slot, hi - lo, p0,
                                  since());
@@ -3587,6 +3753,8 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             const double d0 = since();
             try {
                 ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, bandedPoa, sub, order, out, &chunks[c]);
+                if (rich)
+                    for (int z : chunks[c].pinZ) chunks[c].prich.push_back(rich[z]);
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d draft zmws %zu %.1f-%.1f ms\n", c, chunks[c].zs.size(), d0,
                                  since());
@@ -3630,7 +3798,8 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 std::vector<pbccs_window_info> cinfo;
                 if (info)
                     for (int q = 0; q < m; ++q) cinfo.push_back(info[C.pinZ[q]]);
-                rcDraft = polish_windowed_impl(eng, C.pin.data(), m, o, *win, C.pout.data(), info ? cinfo.data() : nullptr);
+                rcDraft = polish_windowed_impl(eng, C.pin.data(), m, o, *win, C.pout.data(), info ? cinfo.data() : nullptr,
+                                               rich ? C.prich.data() : nullptr);
                 if (rcDraft != PBCCS_OK) errDraft = g_lastError;
                 else if (info)
                     for (int q = 0; q < m; ++q) info[C.pinZ[q]] = cinfo[q];
@@ -3655,7 +3824,8 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             }
             CcsChunk& C = chunks[c];
             bind_polish_outputs(&C, out);
-            const int r = polish_retry(eng, 0, C.pin.data(), (int)C.pin.size(), &o, C.pout.data());
+            const int r = polish_retry(eng, 0, C.pin.data(), (int)C.pin.size(), &o, C.pout.data(), nullptr, nullptr,
+                                       nullptr, rich ? C.prich.data() : nullptr);
             if (r != PBCCS_OK) return r;
         }
         bool draftRange = false;
@@ -3664,6 +3834,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             for (size_t q = 0; q < C.pinZ.size(); ++q) {
                 const int z = C.pinZ[q];
                 pbccs_zmw_output& po = out[z].polish;
+                if (rich) rich[z] = C.prich[q];
                 int* const arrOut = po.add_read_results;
                 double* const zsOut = po.zscores;
                 po = C.pout[q];
@@ -3725,6 +3896,18 @@ int pbccs_ccs_batch_ex3(pbccs_engine* eng, const pbccs_ccs_input* in, int n, con
     else pbccs_ccs_options_default(&c);
     return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out, win,
                           info);
+}
+
+int pbccs_ccs_batch_ex4(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                        const pbccs_poa_options* poa, const pbccs_window_options* win,
+                        const pbccs_polish_options* opts, const pbccs_polish_extras* extras, pbccs_ccs_output* out,
+                        pbccs_window_info* info)
+{
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out, win,
+                          info, extras ? extras->rich : nullptr);
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ namespace pbccs {
 const char* const kKernelNames[kKernelKinds] = {"k_fill",       "k_suffix",      "k_enumerate", "k_score",
                                                  "k_reduce",     "k_qv",          "k_best_subset", "k_compact",
                                                  "k_fill_tall",  "k_qfill_grp",   "k_qfill_coop", "k_qfill",
-                                                 "k_qscore_mid", "k_qscore_multi", "k_score_wide"};
+                                                 "k_qscore_mid", "k_qscore_multi", "k_score_wide", "k_qv_rich"};
 
 namespace {
 
@@ -2296,12 +2296,13 @@ bool best_subset_certain(const std::vector<Scored>& in, const std::vector<double
 
 void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std::vector<int>* converged,
                         std::vector<long long>* nTested, std::vector<long long>* nApplied, bool needFinalState,
-                        std::vector<std::vector<int>>* qvsOnConverge)
+                        std::vector<std::vector<int>>* qvsOnConverge, std::vector<RichQVs>* richOnConverge)
 {
     const StreamScope bound(stream_);
     const int n = (int)zl.size();
     converged->assign(n, 0);
     if (qvsOnConverge) qvsOnConverge->assign(n, {});
+    if (qvsOnConverge && richOnConverge) richOnConverge->assign(n, {});
     // ZMWs whose bands nobody reads again once they are done (needFinalState = false: the batch polish reads
     // only converged ZMWs, through their QVs): retired so the reclaiming layout can drop them
     const bool retireDone = reclaim_ && !needFinalState;
@@ -2657,8 +2658,11 @@ void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std
         // bands are dead, so the refill below holds every live read and can lay the value pool out afresh
         if (!qvNow.empty()) {
             std::vector<std::vector<int>> q;
-            QVs(qvNow, &q);
+            std::vector<RichQVs> rq;
+            QVs(qvNow, &q, richOnConverge ? &rq : nullptr);
             for (size_t i = 0; i < qvNow.size(); ++i) (*qvsOnConverge)[qvIdx[i]] = std::move(q[i]);
+            if (richOnConverge)
+                for (size_t i = 0; i < qvNow.size(); ++i) (*richOnConverge)[qvIdx[i]] = std::move(rq[i]);
             if (reclaim_) Retire(qvNow);
         }
         const Clock::time_point t2 = Clock::now();
@@ -2687,7 +2691,7 @@ void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std
 // ------------------------------------------------------------------------------------------------
 // ConsensusQVs
 // ------------------------------------------------------------------------------------------------
-void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* qvs)
+void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich)
 {
     const StreamScope bound(stream_);
     RunRound(zl, nullptr, -std::numeric_limits<double>::max(), true);
@@ -2707,15 +2711,45 @@ void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* 
     W.codes = dCodes_.ptr;
     W.delta = dDelta_.ptr;
     const DevBatch B = View();
-    Timed(kKQv, [&] {
-        launch_qv(B, W, rTotalPos_, dWPosBase_.ptr, dPosOff_.ptr, dScore_.ptr, dWQvBase_.ptr, dQv_.ptr, stream_);
-    });
+    const size_t nPos = (size_t)rTotalPos_;
+    const size_t richInts = 3 * nPos + (2 * nPos + sizeof(int) - 1) / sizeof(int);   // three QV arrays, two tag arrays
+    if (rich) {
+        dRich_.reserve(std::max<size_t>(richInts, 1), false);
+        RichQvOut R;
+        R.sub = dRich_.ptr;
+        R.ins = dRich_.ptr + nPos;
+        R.del = dRich_.ptr + 2 * nPos;
+        R.subTag = reinterpret_cast<char*>(dRich_.ptr + 3 * nPos);
+        R.insTag = R.subTag + nPos;
+        Timed(kKQvRich, [&] {
+            launch_qv_rich(B, W, rTotalPos_, dWPosBase_.ptr, dPosOff_.ptr, dScore_.ptr, dWQvBase_.ptr, dQv_.ptr, R,
+                           stream_);
+        });
+    } else {
+        Timed(kKQv, [&] {
+            launch_qv(B, W, rTotalPos_, dWPosBase_.ptr, dPosOff_.ptr, dScore_.ptr, dWQvBase_.ptr, dQv_.ptr, stream_);
+        });
+    }
     PBCCS_HIP(hipGetLastError());
-    std::vector<int> q;
+    std::vector<int> q, rq;
     download(q, dQv_, rTotalPos_, stream_);
+    if (rich) download(rq, dRich_, richInts, stream_);
     PBCCS_HIP(hipStreamSynchronize(stream_));
     qvs->assign(zl.size(), {});
     for (size_t k = 0; k < zl.size(); ++k) (*qvs)[k].assign(q.begin() + rPosStart_[k], q.begin() + rPosStart_[k + 1]);
+    if (rich) {
+        rich->assign(zl.size(), {});
+        const char* tags = reinterpret_cast<const char*>(rq.data() + 3 * nPos);
+        for (size_t k = 0; k < zl.size(); ++k) {
+            const long long b = rPosStart_[k], e = rPosStart_[k + 1];
+            RichQVs& r = (*rich)[k];
+            r.subQv.assign(rq.begin() + b, rq.begin() + e);
+            r.insQv.assign(rq.begin() + nPos + b, rq.begin() + nPos + e);
+            r.delQv.assign(rq.begin() + 2 * nPos + b, rq.begin() + 2 * nPos + e);
+            r.subTag.assign(tags + b, tags + e);
+            r.insTag.assign(tags + nPos + b, tags + nPos + e);
+        }
+    }
 }
 
 }  // namespace pbccs

@@ -266,9 +266,10 @@ void ckpt_policy(int* K, int* minLen);
 // The Quiver family's kinds (kKQ*) are the QuiverBatch fills (four reads per wavefront, a wave per read on the side
 // stream, the lane-serial fill) its batched middle-case scoring and the repeat rounds' multi-base scoring (cells = tasks).
 // kKScoreWide: Arrow's scoring of mutations of any width (k_score_wide and k_score_wide_refill; cells = tasks).
+// kKQvRich: k_qv_rich, the QV kernel of a rich-QV call, apart from kKQv's k_qv.
 enum KernelKind {
     kKFill = 0, kKSuffix, kKEnumerate, kKScore, kKReduce, kKQv, kKSelect, kKCompact, kKFillTall,
-    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKScoreWide, kKernelKinds
+    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKScoreWide, kKQvRich, kKernelKinds
 };
 extern const char* const kKernelNames[kKernelKinds];
 
@@ -376,7 +377,7 @@ public:
     // per listed ZMW (empty for the ones that do not converge); with reclaim on, their bands are then dropped.
     void Refine(const std::vector<int>& zmws, const RefineOptions& ro, std::vector<int>* converged,
                 std::vector<long long>* nTested, std::vector<long long>* nApplied, bool needFinalState = true,
-                std::vector<std::vector<int>>* qvsOnConverge = nullptr);
+                std::vector<std::vector<int>>* qvsOnConverge = nullptr, std::vector<RichQVs>* richOnConverge = nullptr);
     // Band reclaim (batch polish): a fill whose list holds every read with live bands lays the value pool out
     // afresh from offset 0, each region sized from the read's last band.  Live = filled, active
     // and not retired; the caller retires the ZMWs whose bands it will not read again.
@@ -390,8 +391,9 @@ public:
     // LL bound of `threshold` are re-filled exactly before FinishAddRead decides.
     void CertifyAddReads(const std::vector<int>& reads, double threshold);
     void Retire(const std::vector<int>& zmws);
-    // ConsensusQVs for the listed ZMWs.
-    void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs);
+    // ConsensusQVs for the listed ZMWs.  rich != nullptr: the same sweep, then k_qv_rich instead of k_qv: the same
+    // qvs and the per-type QVs and tags of every position.
+    void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich = nullptr);
     // ApplyMutations (MultiReadMutationScorer.cpp:235-267).  Returns false on an invalid edit.
     bool ApplyMutations(int z, const std::vector<Mutation>& muts);
     // ---- mutations of any width (k_score_wide) -------------------------------------------
@@ -590,6 +592,7 @@ private:
     DevVec<float> dSite_;        // the site tensor (SiteScoresDevice)
     DevVec<WideTask> dWide_;     // the task list of k_score_wide and k_score_wide_refill and its deltas (ScoreWide)
     DevVec<double> dWideDelta_;
+    DevVec<int> dRich_;          // k_qv_rich's three QV arrays and, behind them, its two tag arrays
     int wideRows_ = 64;          // band values per column a refill of k_score_wide_refill may take (grown on overflow)
     DiploidScratch diploid_;
     struct Pending {

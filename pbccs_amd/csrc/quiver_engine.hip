@@ -1489,7 +1489,7 @@ void QuiverBatch::RefineRepeatsMany(const std::vector<int>& zs, int repeatLength
     refine_repeats_lockstep(ops, zs, repeatLength, minRepeatElements, ro, nTested, nApplied, converged, status);
 }
 
-std::vector<std::vector<int>> QuiverBatch::QVsMany(const std::vector<int>& zs)   // ConsensusQVs (:274-295)
+std::vector<std::vector<int>> QuiverBatch::QVsMany(const std::vector<int>& zs, std::vector<RichQVs>* rich)   // ConsensusQVs (:274-295)
 {
     // every unique single-base mutation of every position, scored over all reads (Score, no fast break), then the
     // per-position sums and QVs on the device (k_qqv); only the QVs come back
@@ -1541,17 +1541,33 @@ std::vector<std::vector<int>> QuiverBatch::QVsMany(const std::vector<int>& zs)  
     Q.score = dMScore_.ptr;
     Q.qv = dQv_.ptr;
     Q.hostAll = std::getenv("PBCCS_QQV_HOST") != nullptr;   // test hook: the host path for every position
-    launch_qqv(Q, nPos, stream_);
+    const size_t np = (size_t)nPos;
+    const size_t richInts = 3 * np + (2 * np + sizeof(int) - 1) / sizeof(int);
+    if (rich) {
+        dRich_.reserve(std::max<size_t>(richInts, 1), false);
+        QQvRich R;
+        R.codes = dCodes_.ptr;
+        R.sub = dRich_.ptr;
+        R.ins = dRich_.ptr + np;
+        R.del = dRich_.ptr + 2 * np;
+        R.subTag = reinterpret_cast<char*>(dRich_.ptr + 3 * np);
+        R.insTag = R.subTag + np;
+        launch_qqv_rich(Q, R, nPos, stream_);
+    } else {
+        launch_qqv(Q, nPos, stream_);
+    }
     QHIP(hipGetLastError());
-    std::vector<int> all;
+    std::vector<int> all, rq;
     get(all, dQv_, (size_t)nPos, stream_);
+    if (rich) get(rq, dRich_, richInts, stream_);
     QHIP(hipStreamSynchronize(stream_));
     // positions k_qqv left to the host (-1: the rounding of -10 log10(prob) could depend on the libm): their
     // mutation scores come back and the sum, ProbabilityToQV and the libm are the reference's
     std::vector<std::pair<int, int>> amb;   // (scorer, position)
     for (int w = 0; w < n; ++w)
         for (long long g = posStart[w]; g < posStart[w + 1]; ++g)
-            if (all[(size_t)g] < 0) amb.emplace_back(w, (int)(g - posStart[w]));
+            if (all[(size_t)g] < 0 || (rich && (rq[(size_t)g] < 0 || rq[np + (size_t)g] < 0 || rq[2 * np + (size_t)g] < 0)))
+                amb.emplace_back(w, (int)(g - posStart[w]));
     static const bool qtrace = std::getenv("PBCCS_QUIVER_TRACE") != nullptr;
     if (qtrace) std::fprintf(stderr, "[quiver] qvs positions %lld host-recomputed %zu\n", nPos, amb.size());
     if (!amb.empty()) {   // packed on the device (k_qgather), one download
@@ -1572,13 +1588,40 @@ std::vector<std::vector<int>> QuiverBatch::QVsMany(const std::vector<int>& zs)  
         get(sc, dAmbScore_, (size_t)dst[na], stream_);
         QHIP(hipStreamSynchronize(stream_));
         par_for(na, [&](int a) {   // (a fifth of the positions at 10 passes: the high QVs sit near prob ~ eps)
-            double sum = 0.0;
-            for (long long m = dst[a]; m < dst[a + 1]; ++m) {
-                const double f = (double)(float)sc[(size_t)m];   // Score() is a float sum
-                if (f < 0.0) sum += std::exp(f);
+            const size_t g = (size_t)(posStart[amb[a].first] + amb[a].second);
+            if (all[g] < 0) {
+                double sum = 0.0;
+                for (long long m = dst[a]; m < dst[a + 1]; ++m) {
+                    const double f = (double)(float)sc[(size_t)m];   // Score() is a float sum
+                    if (f < 0.0) sum += std::exp(f);
+                }
+                all[g] = probability_to_qv(1.0 - 1.0 / (1.0 + sum));
             }
-            all[(size_t)(posStart[amb[a].first] + amb[a].second)] = probability_to_qv(1.0 - 1.0 / (1.0 + sum));
+            if (!rich) return;
+            // the typed QVs k_qqv_rich left to the host: the partial sums by mutation type, in enumeration order
+            const int* code = codes[amb[a].first].data() + (posOff.data() + posOffBase[amb[a].first])[amb[a].second];
+            double part[3] = {0.0, 0.0, 0.0};   // 0 insertion, 1 deletion, 2 substitution
+            for (long long m = dst[a]; m < dst[a + 1]; ++m) {
+                const double f = (double)(float)sc[(size_t)m];
+                if (f < 0.0) part[mut_type(code[m - dst[a]])] += std::exp(f);
+            }
+            int* typed[3] = {&rq[np + g], &rq[2 * np + g], &rq[g]};   // ins, del, sub
+            for (int t = 0; t < 3; ++t)
+                if (*typed[t] < 0) *typed[t] = probability_to_qv(1.0 - 1.0 / (1.0 + part[t]));
         }, 4096);
+    }
+    if (rich) {
+        rich->assign(n, {});
+        const char* tags = reinterpret_cast<const char*>(rq.data() + 3 * np);
+        for (int w = 0; w < n; ++w) {
+            const long long b = posStart[w], e = posStart[w + 1];
+            RichQVs& r = (*rich)[w];
+            r.subQv.assign(rq.begin() + b, rq.begin() + e);
+            r.insQv.assign(rq.begin() + np + b, rq.begin() + np + e);
+            r.delQv.assign(rq.begin() + 2 * np + b, rq.begin() + 2 * np + e);
+            r.subTag.assign(tags + b, tags + e);
+            r.insTag.assign(tags + np + b, tags + np + e);
+        }
     }
     std::vector<std::vector<int>> qv(n);
     for (int w = 0; w < n; ++w) qv[w].assign(all.begin() + posStart[w], all.begin() + posStart[w + 1]);

@@ -143,7 +143,9 @@ public:
     // one refill per round.  ok[k] = 0 where ApplyMutations refused an edit (the scorer's Refine returns false).
     void RefineMany(const std::vector<int>& zs, const RefineOptions& ro, std::vector<long long>* nTested,
                     std::vector<long long>* nApplied, std::vector<char>* converged, std::vector<char>* ok);
-    std::vector<std::vector<int>> QVsMany(const std::vector<int>& zs);
+    // rich != nullptr: k_qqv_rich instead of k_qqv after the same sweep: the same QVs and the per-type QVs and tags
+    // of every position, the typed QVs under k_qqv's rule too (the host's libm where it matters)
+    std::vector<std::vector<int>> QVsMany(const std::vector<int>& zs, std::vector<RichQVs>* rich = nullptr);
     // RecursorBase::Alignment (detail/RecursorBase.cpp:124-264) of read r against its template window,
     // from the read's alpha band (Viterbi configs only): the gapped target and query strings.
     bool Alignment(int r, std::string* target, std::string* query);
@@ -265,6 +267,7 @@ private:
     DevVec<unsigned long long> dEdgeCount_;
     DevVec<long long> dPosStart_, dPosOffBase_;   // QVsMany: per-position QVs on the device (k_qqv)
     DevVec<long long> dAmbSrc_, dAmbDst_;         // QVsMany: the positions left to the host (k_qgather)
+    DevVec<int> dRich_;                           // QVsMany: k_qqv_rich's three QV arrays, then its two tag arrays
     DevVec<double> dAmbScore_;
     DevVec<int> dPosOff_, dQv_;
     DevVec<int> dWReadBase_, dWNReads_, dReadList_, dRActive_, dSelCode_, dSelRank_, dNSel_;

@@ -2403,6 +2403,90 @@ __global__ void __launch_bounds__(256) k_qqv(QQvWork W, long long nPos)
     W.qv[g] = amb ? -1 : (int)round(v);
 }
 
+// k_qqv's rule for one sum of `terms` terms: the QV, or -1 where its rounding could depend on the libm.  The bound
+// follows the terms summed: an ulp per term and per partial sum (k_qqv takes 16 for its up to nine).
+__device__ __forceinline__ int qqv_certified(double sum, int terms, bool hostAll)
+{
+    constexpr double eps = 2.220446049250313e-16;
+    double prob = 1.0 - 1.0 / (1.0 + sum);
+    bool amb = hostAll;
+    double rel = 0.0;
+    if (prob == 0.0) {
+        amb = amb || sum > 0.4 * eps;
+        prob = 2.2250738585072014e-308;   // std::numeric_limits<double>::min()
+    } else {
+        rel = (4.0 * eps + 2.0 * terms * eps * sum) / prob;
+    }
+    const double v = -10.0 * log10(prob);
+    const double frac = v - floor(v);
+    amb = amb || fabs(frac - 0.5) < 4.35 * rel + 1e-6;
+    return amb ? -1 : (int)round(v);
+}
+
+// ---- k_qqv_rich: k_qqv plus the per-type QVs and tags of each position ---------------------
+// qv is k_qqv's, statement for statement.  The three typed QVs follow the same rule on the partial sums over the
+// position's substitutions, insertions and deletion (enumeration order), each -1 where the host must recompute it
+// (QuiverBatch::QVsMany packs those positions' scores with k_qgather).  The tags compare the float scores, so they
+// need no such care: the first maximum in enumeration order, scores >= 0 included.
+__global__ void __launch_bounds__(256) k_qqv_rich(QQvWork W, QQvRich R, long long nPos)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nPos) return;
+    int lo = 0, hi = W.nWork;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (W.posStart[mid] <= g) lo = mid; else hi = mid;
+    }
+    const int p = (int)(g - W.posStart[lo]);
+    const int* po = W.posOff + W.posOffBase[lo];
+    const double* sc = W.score + W.wMutStart[lo];
+    const int* code = R.codes + W.wMutStart[lo];
+    double sum = 0.0;
+    for (int m = po[p]; m < po[p + 1]; ++m) {
+        const double s = (double)(float)sc[m];   // Score() is a float sum
+        if (s < 0.0) sum += exp(s);
+    }
+    constexpr double eps = 2.220446049250313e-16;
+    double prob = 1.0 - 1.0 / (1.0 + sum);
+    bool amb = W.hostAll != 0;
+    double rel = 0.0;
+    if (prob == 0.0) {
+        amb = amb || sum > 0.4 * eps;
+        prob = 2.2250738585072014e-308;   // std::numeric_limits<double>::min()
+    } else {
+        rel = (4.0 * eps + 16.0 * eps * sum) / prob;
+    }
+    const double v = -10.0 * log10(prob);
+    const double frac = v - floor(v);
+    amb = amb || fabs(frac - 0.5) < 4.35 * rel + 1e-6;
+    W.qv[g] = amb ? -1 : (int)round(v);
+
+    double part[3] = {0.0, 0.0, 0.0};   // by mutation type: 0 insertion, 1 deletion, 2 substitution
+    int terms[3] = {0, 0, 0};
+    double bestSub = 0.0, bestIns = 0.0;
+    int tagSub = -1, tagIns = -1;
+    for (int m = po[p]; m < po[p + 1]; ++m) {
+        const double s = (double)(float)sc[m];
+        const int c = code[m];
+        const int type = (c >> 2) & 3;
+        const bool neg = s < 0.0;
+        const double e = neg ? exp(s) : 0.0;
+        part[0] += type == 0 ? e : 0.0;
+        part[1] += type == 1 ? e : 0.0;
+        part[2] += type == 2 ? e : 0.0;
+        terms[0] += (type == 0 && neg) ? 1 : 0;
+        terms[1] += (type == 1 && neg) ? 1 : 0;
+        terms[2] += (type == 2 && neg) ? 1 : 0;
+        if (type == 2 && (tagSub < 0 || s > bestSub)) { bestSub = s; tagSub = c & 3; }
+        if (type == 0 && (tagIns < 0 || s > bestIns)) { bestIns = s; tagIns = c & 3; }
+    }
+    R.ins[g] = qqv_certified(part[0], terms[0], W.hostAll != 0);
+    R.del[g] = qqv_certified(part[1], terms[1], W.hostAll != 0);
+    R.sub[g] = qqv_certified(part[2], terms[2], W.hostAll != 0);
+    R.subTag[g] = tagSub < 0 ? 'N' : "ACGT"[tagSub];
+    R.insTag[g] = tagIns < 0 ? 'N' : "ACGT"[tagIns];
+}
+
 // ---- k_qgather: the mutation scores of the positions k_qqv left to the host, packed for one download ---------
 __global__ void __launch_bounds__(256) k_qgather(const double* __restrict__ score, const long long* __restrict__ src,
                                                  const long long* __restrict__ dst, int n, double* __restrict__ out)
@@ -2544,6 +2628,12 @@ void launch_qqv(const QQvWork& W, long long nPos, hipStream_t s)
 {
     if (nPos <= 0) return;
     hipLaunchKernelGGL(k_qqv, dim3((unsigned)((nPos + 255) / 256)), dim3(256), 0, s, W, nPos);
+}
+
+void launch_qqv_rich(const QQvWork& W, const QQvRich& R, long long nPos, hipStream_t s)
+{
+    if (nPos <= 0) return;
+    hipLaunchKernelGGL(k_qqv_rich, dim3((unsigned)((nPos + 255) / 256)), dim3(256), 0, s, W, R, nPos);
 }
 
 void launch_qgather(const double* score, const long long* src, const long long* dst, int n, double* out, hipStream_t s)

@@ -153,6 +153,17 @@ struct QQvWork {
     int hostAll = 0;               // test hook (PBCCS_QQV_HOST=1): every position left to the host
 };
 void launch_qqv(const QQvWork& W, long long nPos, hipStream_t s);
+// k_qqv_rich's extra input and outputs: the round's mutation codes (beside score[]) and, per
+// global position, the substitution / insertion / deletion QVs (-1: left to the host, as qv) and the two tags.
+struct QQvRich {
+    const int* codes;
+    int* sub;
+    int* ins;
+    int* del;
+    char* subTag;
+    char* insTag;
+};
+void launch_qqv_rich(const QQvWork& W, const QQvRich& R, long long nPos, hipStream_t s);
 // QVsMany's host path: out[dst[a] .. dst[a + 1]) = score[src[a] ..], one thread per position a (n positions)
 void launch_qgather(const double* score, const long long* src, const long long* dst, int n, double* out, hipStream_t s);
 

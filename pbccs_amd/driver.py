@@ -185,7 +185,7 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
-              polish_window=None):
+              polish_window=None, rich_qvs=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -202,6 +202,8 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     overlap, guard, k (polish.polish_windowed's defaults for the rest): drafts longer than window + overlap are
     polished in overlapping windows and stitched.  The results then also carry "n_windows", "windowed" and
     "fallback" (polish.WINDOW_FALLBACK names the codes).
+    rich_qvs (pbccs_ccs_batch_ex4): the results also carry sub_qv, ins_qv, del_qv, sub_tag and ins_tag, the per-base
+    rich QVs of the consensus (pbccs_amd.richqv), as polish_zmws(..., rich_qvs=True) gives them.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -263,7 +265,33 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     opts = settings._c()
     mc = 2**62 if max_poa_coverage is None else int(max_poa_coverage)
     winfo = None
-    if polish_window is not None:
+    rich = None
+    if rich_qvs:   # one pbccs_rich_qvs per ZMW over shared arrays laid out like qv
+        total = max(1, int(cstart[-1]))
+        rich_qv = np.zeros((3, total), dtype=np.int32)
+        rich_tag = np.zeros((2, total), dtype=np.uint8)
+        rich = np.zeros(max(1, n), dtype=_struct_dtype(L.CRichQvs))
+        if n:
+            for row, key in enumerate(("sub_qv", "ins_qv", "del_qv")):
+                rich[key][:n] = rich_qv[row].ctypes.data + 4 * cstart[:-1]
+            for row, key in enumerate(("sub_tag", "ins_tag")):
+                rich[key][:n] = rich_tag[row].ctypes.data + cstart[:-1]
+            rich["cap"][:n] = caps
+        x = L.CPolishExtras()
+        x.rich = ctypes.cast(rich.ctypes.data, ctypes.POINTER(L.CRichQvs))
+        wo = None
+        if polish_window is not None:
+            from .polish import window_options
+            wo = window_options(**dict(polish_window))
+            winfo = (L.CWindowInfo * max(1, n))()
+        co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
+        po = L.CPoaOptions(mc, -1, 1 if banded_poa else 0)
+        L.check(L.load().pbccs_ccs_batch_ex4(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                             ctypes.byref(co), ctypes.byref(po),
+                                             ctypes.byref(wo) if wo is not None else None, ctypes.byref(opts),
+                                             ctypes.byref(x), ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput)),
+                                             winfo))
+    elif polish_window is not None:
         from .polish import window_options
         wo = window_options(**dict(polish_window))
         winfo = (L.CWindowInfo * max(1, n))()
@@ -311,4 +339,11 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
                     "n_applied": nappl[z], "n_passes": npass[z], "status_counts": scounts[z]})
         if winfo is not None:
             res[-1].update(n_windows=winfo[z].n_windows, windowed=winfo[z].n_windows > 1, fallback=winfo[z].fallback)
+        if rich is not None:
+            rl = int(rich["len"][z])
+            if rl < 0:
+                raise L.PbccsError(-5, "rich QVs outgrew their buffers")
+            res[-1].update(sub_qv=rich_qv[0, c:c + rl].tolist(), ins_qv=rich_qv[1, c:c + rl].tolist(),
+                           del_qv=rich_qv[2, c:c + rl].tolist(), sub_tag=rich_tag[0, c:c + rl].tobytes().decode(),
+                           ins_tag=rich_tag[1, c:c + rl].tobytes().decode())
     return res

@@ -269,6 +269,17 @@ class CWindowStats(ctypes.Structure):
                 ("polish_ms", ctypes.c_double), ("join_ms", ctypes.c_double), ("fallback_ms", ctypes.c_double)]
 
 
+class CRichQvs(ctypes.Structure):
+    _fields_ = [("sub_qv", ctypes.POINTER(ctypes.c_int)), ("ins_qv", ctypes.POINTER(ctypes.c_int)),
+                ("del_qv", ctypes.POINTER(ctypes.c_int)), ("sub_tag", ctypes.POINTER(ctypes.c_char)),
+                ("ins_tag", ctypes.POINTER(ctypes.c_char)), ("cap", ctypes.c_int), ("len", ctypes.c_int)]
+
+
+class CPolishExtras(ctypes.Structure):
+    _fields_ = [("repeats", ctypes.POINTER(CRepeatOptions)), ("repeat_tested", ctypes.POINTER(ctypes.c_longlong)),
+                ("repeat_applied", ctypes.POINTER(ctypes.c_longlong)), ("rich", ctypes.POINTER(CRichQvs))]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -421,6 +432,12 @@ SIGNATURES = {
                                   ctypes.POINTER(CWindowOptions), ctypes.POINTER(CZmwOutput),
                                   ctypes.POINTER(CWindowInfo)]),
     "pbccs_window_stats_get": (I, [P, ctypes.POINTER(CWindowStats), I]),
+    # per-base rich QVs
+    "pbccs_consensus_qvs_rich": (I, [P, PI, ctypes.POINTER(CRichQvs), PI]),
+    "pbccs_quiver_consensus_qvs_rich": (I, [P, PI, ctypes.POINTER(CRichQvs), PI]),
+    "pbccs_polish_windowed_ex": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
+                                     ctypes.POINTER(CWindowOptions), ctypes.POINTER(CPolishExtras),
+                                     ctypes.POINTER(CZmwOutput), ctypes.POINTER(CWindowInfo)]),
 }
 # bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
 DIGIT_SIGNATURES = {
@@ -431,6 +448,15 @@ DIGIT_SIGNATURES = {
                                 ctypes.POINTER(CPoaOptions), ctypes.POINTER(CWindowOptions),
                                 ctypes.POINTER(CPolishOptions), ctypes.POINTER(CCcsOutput),
                                 ctypes.POINTER(CWindowInfo)]),
+    "pbccs_polish_batch_ex2": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
+                                   ctypes.POINTER(CPolishExtras), ctypes.POINTER(CZmwOutput)]),
+    "pbccs_quiver_polish_batch_ex2": (I, [P, ctypes.POINTER(CQuiverConfig), ctypes.POINTER(ctypes.c_char_p), I,
+                                          ctypes.POINTER(CQuiverZmw), I, ctypes.POINTER(CRefineOptions),
+                                          ctypes.POINTER(CPolishExtras), ctypes.POINTER(CQuiverResult)]),
+    "pbccs_ccs_batch_ex4": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                                ctypes.POINTER(CPoaOptions), ctypes.POINTER(CWindowOptions),
+                                ctypes.POINTER(CPolishOptions), ctypes.POINTER(CPolishExtras),
+                                ctypes.POINTER(CCcsOutput), ctypes.POINTER(CWindowInfo)]),
 }
 
 

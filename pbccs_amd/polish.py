@@ -146,30 +146,53 @@ def polish_many(batches):
     L.check(batches[0]._lib.pbccs_batch_polish_many(hs, n, outs))
 
 
-def _polish_repeats(zmws, settings, engine, repeats, one_batch):
+def _rich_buffers(m):
+    """RichBuffers for the ZMWs of a _Marshalled, each as large as the ZMW's consensus buffer."""
+    from .richqv import RichBuffers
+    return RichBuffers([o.consensus_cap for o in m._outs[:len(m.zmws)]])
+
+
+def _add_rich(res, rb):
+    """The five rich keys into the records; empty for a ZMW without a consensus."""
+    for i, r in enumerate(res):
+        r.update(rb.record(i))
+    return res
+
+
+def _polish_repeats(zmws, settings, engine, repeats, one_batch, rich_qvs=False):
     """pbccs_polish_batch_ex: RefineConsensus, RefineRepeats(repeat_length, min_repeat_elements), ConsensusQVs per
-    ZMW; the records gain n_repeat_tested / n_repeat_applied."""
+    ZMW; the records gain n_repeat_tested / n_repeat_applied.  rich_qvs (with or without
+    repeats): pbccs_polish_batch_ex2 with one pbccs_rich_qvs per ZMW."""
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
-    repeat_length, min_repeat_elements = repeats
     m = _Marshalled(zmws)
     n = len(zmws)
     opts = settings._c()
     if one_batch and opts.zmws_per_batch <= 0:
         opts.zmws_per_batch = max(1, n)   # polish_zmws: one device batch
-    ro = L.CRepeatOptions(int(repeat_length), int(min_repeat_elements), 1, 10, 20)
-    rt = (ctypes.c_longlong * max(1, n))()
-    ra = (ctypes.c_longlong * max(1, n))()
-    L.check(L.load().pbccs_polish_batch_ex(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(ro), rt, ra, m._outs))
+    ro = rt = ra = None
+    if repeats is not None:
+        repeat_length, min_repeat_elements = repeats
+        ro = L.CRepeatOptions(int(repeat_length), int(min_repeat_elements), 1, 10, 20)
+        rt = (ctypes.c_longlong * max(1, n))()
+        ra = (ctypes.c_longlong * max(1, n))()
+    if rich_qvs:
+        rb = _rich_buffers(m)
+        x = rb.extras(ro, rt, ra)
+        L.check(L.load().pbccs_polish_batch_ex2(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(x), m._outs))
+    else:
+        L.check(L.load().pbccs_polish_batch_ex(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(ro), rt, ra,
+                                               m._outs))
     res = m.results()
-    for i, r in enumerate(res):
-        r["n_repeat_tested"] = rt[i]
-        r["n_repeat_applied"] = ra[i]
-    return res
+    if repeats is not None:
+        for i, r in enumerate(res):
+            r["n_repeat_tested"] = rt[i]
+            r["n_repeat_applied"] = ra[i]
+    return _add_rich(res, rb) if rich_qvs else res
 
 
-def polish_zmws(zmws, settings=None, engine=None, repeats=None):
+def polish_zmws(zmws, settings=None, engine=None, repeats=None, rich_qvs=False):
     """Polish ZMWs on the GPU (upload, hot path, download).
 
     zmws: list of dicts {draft, snr (4), reads: [{seq, strand, ts, te, full_pass?}]}.
@@ -177,9 +200,11 @@ def polish_zmws(zmws, settings=None, engine=None, repeats=None):
     n_tested, n_applied, n_passes, status_counts.
     repeats=(repeat_length, min_repeat_elements): RefineRepeats between RefineConsensus and ConsensusQVs
     (pbccs_polish_batch_ex); the records then also hold n_repeat_tested and n_repeat_applied.
+    rich_qvs=True: the records also hold sub_qv, ins_qv, del_qv, sub_tag and ins_tag, the per-base rich QVs of the
+    final template (pbccs_polish_batch_ex2; named by mutation type, see pbccs_amd.richqv).
     """
-    if repeats is not None:
-        return _polish_repeats(zmws, settings, engine, repeats, True)
+    if repeats is not None or rich_qvs:
+        return _polish_repeats(zmws, settings, engine, repeats, True, rich_qvs)
     b = PreparedBatch(zmws, settings, engine)
     try:
         b.polish()
@@ -254,13 +279,15 @@ def window_slices(zmws, window=2000, overlap=200, k=6, min_length=10, engine=Non
     return out
 
 
-def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6, engine=None):
+def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6, engine=None, rich_qvs=False):
     """Polish ZMWs with long drafts as overlapping windows (pbccs_polish_windowed).
 
     Results as polish_zmws plus "windowed" (the draft had more than one window), "fallback" (0, or the reason code
     the ZMW was polished whole for; WINDOW_FALLBACK names them), "unanchored_reads" and "windows": per window
     begin, end, join (the draft position it is joined to the next window at, -1 for none), cut_begin / cut_end
-    (its piece of its own consensus), status, n_tested, n_applied."""
+    (its piece of its own consensus), status, n_tested, n_applied.
+    rich_qvs=True: the five rich keys too (pbccs_polish_windowed_ex); the stitched arrays are the same pieces of the
+    windows' arrays as the stitched qvs."""
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
@@ -275,8 +302,17 @@ def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6,
         recs.append((L.CWindowRecord * cap)())
         info[i].windows = recs[-1]
         info[i].windows_cap = cap
-    L.check(L.load().pbccs_polish_windowed(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(wo), m._outs, info))
+    if rich_qvs:
+        rb = _rich_buffers(m)
+        x = rb.extras()
+        L.check(L.load().pbccs_polish_windowed_ex(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(wo),
+                                                  ctypes.byref(x), m._outs, info))
+    else:
+        L.check(L.load().pbccs_polish_windowed(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(wo), m._outs,
+                                               info))
     res = m.results()
+    if rich_qvs:
+        _add_rich(res, rb)
     for i, r in enumerate(res):
         r["windowed"] = info[i].n_windows > 1
         r["fallback"] = info[i].fallback
@@ -315,12 +351,13 @@ def plan_batches(zmws, budget_bytes, max_per_batch=2000, max_len_ratio=1.5):
     return [list(order[start[b]:start[b + 1]]) for b in range(nb.value)], list(est[:n])
 
 
-def polish_stream(zmws, settings=None, engine=None, repeats=None):
+def polish_stream(zmws, settings=None, engine=None, repeats=None, rich_qvs=False):
     """Polish a stream of heterogeneous ZMWs (pbccs_polish_batch): bucketed by length and pass count into
     memory-sized device batches that the engine's workspace slots pull largest-first from one queue, like
-    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws(); `repeats` as there."""
-    if repeats is not None:
-        return _polish_repeats(zmws, settings, engine, repeats, False)
+    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws(); `repeats` and
+    `rich_qvs` as there."""
+    if repeats is not None or rich_qvs:
+        return _polish_repeats(zmws, settings, engine, repeats, False, rich_qvs)
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()

@@ -582,14 +582,27 @@ class PreparedQuiverBatch:
         self.__dict__.update(dict(keep=keep, carr=carr, names=names, nc=nc, cz=cz, res=res, n=n, cap=cap,
                                   cstart=cstart, cons=cons, qvb=qvb, qvs=qvs))
 
-    def run(self, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, engine=None, repeats=None):
+    def run(self, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, engine=None, repeats=None,
+            rich_qvs=False):
         from . import default_engine
         eng = engine or default_engine()
         carr, names, nc, cz, res, n = self.carr, self.names, self.nc, self.cz, self.res, self.n
         cap, cstart, cons, qvb, qvs = self.cap, self.cstart, self.cons, self.qvb, self.qvs
         o = _lib_mod.CRefineOptions(max_iterations, mutation_separation, mutation_neighborhood)
-        rep_t = rep_a = None
-        if repeats is None:
+        rep_t = rep_a = rb = None
+        if rich_qvs:   # pbccs_quiver_polish_batch_ex2: the rich QVs beside the QVs
+            from .richqv import RichBuffers
+            rb = RichBuffers(cap.tolist())
+            ro = None
+            if repeats is not None:
+                ro = _lib_mod.CRepeatOptions(*(tuple(repeats) + (3, 1, 10, 20)[len(repeats) - 1:]))
+                rep_t = (ctypes.c_longlong * max(1, n))()
+                rep_a = (ctypes.c_longlong * max(1, n))()
+            x = rb.extras(ro, rep_t, rep_a)
+            _lib_mod.check(load().pbccs_quiver_polish_batch_ex2(
+                eng._h, carr, names, nc, ctypes.cast(cz.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverZmw)), n,
+                ctypes.byref(o), ctypes.byref(x), ctypes.cast(res.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverResult))))
+        elif repeats is None:
             _lib_mod.check(load().pbccs_quiver_polish_batch(
                 eng._h, carr, names, nc, ctypes.cast(cz.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverZmw)), n,
                 ctypes.byref(o), ctypes.cast(res.ctypes.data, ctypes.POINTER(_lib_mod.CQuiverResult))))
@@ -621,11 +634,13 @@ class PreparedQuiverBatch:
             if rep_t is not None:
                 out[-1]["repeat_tested"] = rep_t[k]
                 out[-1]["repeat_applied"] = rep_a[k]
+            if rb is not None:
+                out[-1].update(rb.record(k))
         return out
 
 
 def polish_batch(zmws, configs, max_iterations=40, mutation_separation=10, mutation_neighborhood=20, qvs=True,
-                 engine=None, repeats=None):
+                 engine=None, repeats=None, rich_qvs=False):
     """Many Quiver scorers at once (pbccs_quiver_polish_batch): per ZMW, create the scorer over `configs`,
     AddRead every read, RefineConsensus and (qvs) ConsensusQVs -- the per-scorer call sequence, with the
     scorers' rounds in lock-step on the device.
@@ -633,6 +648,7 @@ def polish_batch(zmws, configs, max_iterations=40, mutation_separation=10, mutat
     zmws: [{"tpl", "reads": [{"seq", "strand", "ts", "te", "features": {ins, subs, del, del_tag, merge},
     "chemistry"?}]}].  Returns per ZMW {"consensus", "qvs", "n_tested", "n_applied", "converged", "ok",
     "n_active"}.  repeats=(repeat_length, min_repeat_elements) runs RefineRepeats between the two
-    (pbccs_quiver_polish_batch_ex) and adds "repeat_tested" / "repeat_applied"."""
+    (pbccs_quiver_polish_batch_ex) and adds "repeat_tested" / "repeat_applied".  rich_qvs=True adds "sub_qv",
+    "ins_qv", "del_qv", "sub_tag", "ins_tag" (pbccs_amd.richqv; empty where ok is false)."""
     return PreparedQuiverBatch(zmws, configs, qvs).run(max_iterations, mutation_separation, mutation_neighborhood,
-                                                        engine, repeats)
+                                                        engine, repeats, rich_qvs)
