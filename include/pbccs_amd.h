@@ -1090,6 +1090,84 @@ int pbccs_ccs_batch_ex4(pbccs_engine* eng, const pbccs_ccs_input* in, int n, con
                         const pbccs_polish_options* opts, const pbccs_polish_extras* extras, pbccs_ccs_output* out,
                         pbccs_window_info* info);
 
+/* ---- consensus kinetics: per-strand mean IPD and pulse width -------------------------
+ * An opt-in with no counterpart in the reference (2015 pbccs has no kinetics); csrc/kinetics_kernels.hpp states
+ * the rules.  Frames are unsigned 16-bit counts.  A read placed on the consensus [tb, te) with its oriented
+ * positions from rb on contributes, for every M or R column of its transcript (target = consensus, query =
+ * oriented read), its frames at original index q (rc == 0) or len - 1 - q (rc != 0); I columns contribute
+ * nothing, D columns leave the position without this read.  Per strand (rc == 0 forward, rc != 0 reverse),
+ * position and track: coverage n, integer sum S, mean (2 S + n) / (2 n) in integer division (0 where n == 0,
+ * at most 65535) and the mean's CodecV1 code.  Forward arrays are indexed by consensus position; entry k of a
+ * reverse array belongs to consensus position consensus_len - 1 - k. */
+#define PBCCS_KIN_USED 0
+#define PBCCS_KIN_UNMAPPED 1       /* MapToDraft did not place the read (or there is no read) */
+#define PBCCS_KIN_EMPTY_EXTENT 2   /* no consensus position or no read position inside the extents */
+#define PBCCS_KIN_ALIGN_FAILED 3   /* the read's alignment did not return PBCCS_OK */
+
+typedef struct {
+    const char* transcript;     /* M R I D */
+    int transcript_len;
+    int rc, rb, tb, te;
+    int len;                    /* the read's length I */
+    const unsigned short* ip;   /* len frames, or NULL: the read has no such track */
+    const unsigned short* pw;
+} pbccs_kinetics_read;
+
+typedef struct {
+    int consensus_len;
+    int n_reads;
+    const pbccs_kinetics_read* reads;
+} pbccs_kinetics_pileup_input;
+
+/* Index 2 * strand + track: forward ipd, forward pw, reverse ipd, reverse pw; consensus_len entries each.  Every
+ * pointer may be NULL.  A read without a track is not counted in that track's coverage, hence one coverage per
+ * track.  n_contributed: fn, rn -- the strand's reads with at least one M or R column and at least one track. */
+typedef struct {
+    unsigned short* mean[4];
+    unsigned char* code[4];
+    int* coverage[4];
+    int n_contributed[2];
+    int* read_status;   /* n_reads PBCCS_KIN_* */
+} pbccs_kinetics_output;
+
+/* k_kin_columns and k_kin_reduce only, on the caller's transcripts.  PBCCS_EINVAL before any device work: a
+ * negative length, a character other than M R I D, a transcript whose target columns are not te - tb or whose
+ * query columns run past len - rb, extents outside [0, consensus_len].  A read with te == tb or without a query
+ * column is skipped as PBCCS_KIN_EMPTY_EXTENT. */
+int pbccs_kinetics_pileup(pbccs_engine* eng, const pbccs_kinetics_pileup_input* in, int n, pbccs_kinetics_output* out);
+
+typedef struct {
+    const char* consensus;
+    int consensus_len;
+    int n_reads;
+    const char* const* seqs;              /* a NULL or zero-length read is PBCCS_KIN_UNMAPPED */
+    const int* lens;
+    const unsigned short* const* ip;      /* NULL, or n_reads pointers: lens[r] frames each, NULL for no track */
+    const unsigned short* const* pw;
+} pbccs_kinetics_input;
+
+typedef struct {
+    pbccs_align_band band;   /* passed to the aligner; PBCCS_BAND_OFF by default */
+} pbccs_kinetics_options;
+void pbccs_kinetics_options_default(pbccs_kinetics_options* o);
+
+/* Per read: pbccs_map_batch's placement on the consensus (min_score_to_add 0), then Align (NW, 0 -1 -1 -1) of
+ * consensus[tb, te) and the oriented read's [rb, re), then the pileup, in one native call; the transcripts pass
+ * through host memory between the aligner and the pileup.  opts NULL is the defaults.  A read that is not mapped,
+ * whose extent is empty or whose alignment fails is skipped with its status and does not fail the call.
+ * PBCCS_EINVAL before any device work: an empty consensus, a negative length, a NULL read with a positive length,
+ * a consensus or read longer than 65535, an unknown band mode. */
+int pbccs_kinetics_batch(pbccs_engine* eng, const pbccs_kinetics_input* in, int n, const pbccs_kinetics_options* opts,
+                         pbccs_kinetics_output* out);
+
+/* Kinetics work since the last reset: reads given, reads skipped by reason, transcript columns walked, (ZMW,
+ * strand, position) threads of the reduction, kernel launches, device ms per kernel (profiling on). */
+typedef struct {
+    long long reads, skipped_unmapped, skipped_empty_extent, skipped_align_failed, columns, positions, launches;
+    double columns_ms, reduce_ms;
+} pbccs_kinetics_stats;
+int pbccs_kinetics_stats_get(pbccs_engine* eng, pbccs_kinetics_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

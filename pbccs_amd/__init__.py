@@ -369,6 +369,8 @@ from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac,
                     TargetToQueryPositions, UnsupportedFeatureError, align_band_stats, align_batch, align_stats)
 from .mapping import map_batch, map_stats, map_to_draft  # noqa: E402,F401
 from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa: E402,F401
+from .kinetics import (codec_v1_decode, codec_v1_encode, kinetics_batch, kinetics_pileup,  # noqa: E402,F401
+                       kinetics_stats)
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -280,7 +280,9 @@ def _tag_dict(tags):
 def read_subread_bam(path):
     """Subread records as ccs.cpp:402-475 reads them through pbbam: [{name, seq, hole, qs, qe, snr, flags,
     read_score}] in file order (name = movie/hole/qs_qe; snr from `sn`, flags from `cx`, read score from
-    `rq`, defaults when a tag is absent: full pass, score 1.0)."""
+    `rq`, defaults when a tag is absent: full pass, score 1.0).  A record with `ip` / `pw` tags also carries
+    them as frames: a B:C array holds CodecV1 codes and is decoded, a B:S array holds frames as they are
+    (kinetics.codec_v1_decode); the keys are absent when the tags are."""
     _, lines = read_bam(path)
     out = []
     for line in lines:
@@ -288,7 +290,21 @@ def read_subread_bam(path):
         t = _tag_dict(f[11:])
         out.append({"name": f[0], "seq": "" if f[9] == "*" else f[9], "hole": t.get("zm"), "qs": t.get("qs"),
                     "qe": t.get("qe"), "snr": t.get("sn"), "flags": t.get("cx", 3), "read_score": t.get("rq", 1.0)})
+        for tag in f[11:]:
+            if tag[:5] in ("ip:B:", "pw:B:"):
+                out[-1][tag[:2]] = _kinetics_frames(tag)
     return out
+
+
+def _kinetics_frames(tag):
+    from .kinetics import codec_v1_decode
+    parts = tag.split(":", 2)[2].split(",")
+    vals = [int(x) for x in parts[1:]]
+    if parts[0] == "C":
+        return codec_v1_decode(vals)
+    if parts[0] == "S":
+        return vals
+    raise ValueError(f"kinetics tag {tag[:2]} of type B:{parts[0]} (B:C codes or B:S frames expected)")
 
 
 def group_subread_bam(path, min_snr=4.0, min_passes=3, min_read_score=0.75):
@@ -301,9 +317,16 @@ def group_subread_bam(path, min_snr=4.0, min_passes=3, min_read_score=0.75):
     for r in recs:
         movie, hole, _, _ = ccsio.parse_subread_name(r["name"])
         first_snr.setdefault((movie, hole), r["snr"])
-    return ccsio.group_zmws([(r["name"], r["seq"]) for r in recs], lambda m, h: first_snr[(m, h)], min_snr,
-                            min_passes, min_read_score, read_score_of=lambda n: by_name[n]["read_score"],
-                            flags_of=lambda n: by_name[n]["flags"])
+    chunks, counts = ccsio.group_zmws([(r["name"], r["seq"]) for r in recs], lambda m, h: first_snr[(m, h)], min_snr,
+                                      min_passes, min_read_score, read_score_of=lambda n: by_name[n]["read_score"],
+                                      flags_of=lambda n: by_name[n]["flags"])
+    for c in chunks:   # the kinetics tracks travel with their reads
+        for rd in c["reads"]:
+            src = by_name[rd["name"]]
+            for key in ("ip", "pw"):
+                if key in src:
+                    rd[key] = src[key]
+    return chunks, counts
 
 
 def write_ccs_bam(path, movies, sam_lines, pbi=False):
@@ -317,12 +340,25 @@ def write_ccs_bam(path, movies, sam_lines, pbi=False):
         write_pbi(path + ".pbi", [pbi_entry(line, off) for line, off in zip(sam_lines, offsets)])
 
 
-def subread_sam_line(movie, hole, qs, qe, seq, snr, flags=3, read_score=0.9, rg="00000000"):
-    """A PacBio subread record as SAM text (the tags ccs.cpp reads), for building test inputs."""
+def subread_sam_line(movie, hole, qs, qe, seq, snr, flags=3, read_score=0.9, rg="00000000", ip=None, pw=None,
+                     kinetics_codec=False):
+    """A PacBio subread record as SAM text (the tags ccs.cpp reads), for building test inputs.  ip / pw: the
+    kinetics tracks in frames, one per base, written as B:S -- or, with kinetics_codec=True, as the B:C CodecV1
+    codes of the frames (lossy above 63)."""
     sn = ",".join(_f32_text(x) for x in snr)
-    return "\t".join([f"{movie}/{hole}/{qs}_{qe}", "4", "*", "0", "255", "*", "*", "0", "0", seq, "*",
-                      f"RG:Z:{rg}", f"zm:i:{hole}", f"qs:i:{qs}", f"qe:i:{qe}", f"sn:B:f,{sn}", f"cx:i:{flags}",
-                      f"rq:f:{_f32_text(read_score)}"])
+    tags = [f"RG:Z:{rg}", f"zm:i:{hole}", f"qs:i:{qs}", f"qe:i:{qe}", f"sn:B:f,{sn}", f"cx:i:{flags}",
+            f"rq:f:{_f32_text(read_score)}"]
+    for name, track in (("ip", ip), ("pw", pw)):
+        if track is None:
+            continue
+        if len(track) != len(seq):
+            raise ValueError(f"{name}: {len(track)} frames for {len(seq)} bases")
+        if kinetics_codec:
+            from .kinetics import codec_v1_encode
+            tags.append(f"{name}:B:C" + "".join(f",{c}" for c in codec_v1_encode(track)))
+        else:
+            tags.append(f"{name}:B:S" + "".join(f",{int(v)}" for v in track))
+    return "\t".join([f"{movie}/{hole}/{qs}_{qe}", "4", "*", "0", "255", "*", "*", "0", "0", seq, "*"] + tags)
 
 
 __all__ = ["BgzfReader", "BgzfWriter", "bam_record_to_sam", "group_subread_bam", "read_bam", "read_subread_bam",

@@ -139,7 +139,7 @@ def _f32(x):
                                                                ("inf" if x > 0 else "-inf"))
 
 
-def ccs_sam_record(movie, hole, result, snr, rich=False):
+def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False):
     """The CCS record of src/main/ccs.cpp:105-172 as a SAM text line (unmapped, flag 4; MAPQ 255).
 
     result: one pbccs_amd polish result (status Success).  Tags in the reference's order: RG zm np rq sn pq
@@ -148,6 +148,9 @@ def ccs_sam_record(movie, hole, result, snr, rich=False):
     Phred+33 strings) and dt st (base strings).  The file format names by error type, the inverse of the record's
     mutation types: dq / dt (DeletionQV / DeletionTag, a base is missing before this one) are
     ins_qv / ins_tag, iq (InsertionQV, this base is spurious) is del_qv, sq / st are sub_qv / sub_tag.
+    kinetics=True (a result made with kinetics=True): the consensus kinetics follow, after the rich tags when both
+    are asked for, as fi fp (forward mean IPD / pulse width, B:C CodecV1 codes), fn (forward passes), ri rp (the
+    same for the reverse strand, in the reverse strand's direction) and rn.
     """
     name = f"{movie}/{hole}/ccs"
     qual = QVsToASCII(result["qvs"])
@@ -167,7 +170,12 @@ def ccs_sam_record(movie, hole, result, snr, rich=False):
     if rich:
         tags += [f"dq:Z:{QVsToASCII(result['ins_qv'])}", f"iq:Z:{QVsToASCII(result['del_qv'])}",
                  f"sq:Z:{QVsToASCII(result['sub_qv'])}", f"dt:Z:{result['ins_tag']}", f"st:Z:{result['sub_tag']}"]
-    fields = [name, "4", "*", "0", "255", "*", "*", "0", "0", result["consensus"] or "*", qual or "*"]
+    if kinetics:
+        def codes(tag, key):
+            return f"{tag}:B:C" + "".join(f",{int(c)}" for c in result[key])
+        tags += [codes("fi", "fwd_ipd"), codes("fp", "fwd_pw"), f"fn:i:{int(result['fn'])}",
+                 codes("ri", "rev_ipd"), codes("rp", "rev_pw"), f"rn:i:{int(result['rn'])}"]
+    fields =[name, "4", "*", "0", "255", "*", "*", "0", "0", result["consensus"] or "*", qual or "*"]
     return "\t".join(fields + tags)
 
 

@@ -26,6 +26,7 @@
 #include "align_kernels.hpp"
 #include "engine.hpp"
 #include "driver.hpp"
+#include "kinetics_kernels.hpp"
 #include "map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
@@ -127,6 +128,15 @@ struct pbccs_engine {
     {
         if (!windowRunner) windowRunner.reset(new window::WindowRunner(device));
         return *windowRunner;
+    }
+    // the kinetics pileup's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<kinetics::KineticsRunner> kineticsRunner;
+    std::mutex kineticsMu;
+    kinetics::KineticsRunner& Kinetics()
+    {
+        if (!kineticsRunner) kineticsRunner.reset(new kinetics::KineticsRunner(device));
+        kineticsRunner->profiling = profiling;
+        return *kineticsRunner;
     }
     Workspace* Slot(int s)
     {
@@ -2772,6 +2782,227 @@ int pbccs_map_stats_get(pbccs_engine* eng, pbccs_map_stats* out, int reset)
         const map::MapStats s = eng->mapper ? eng->mapper->stats : map::MapStats();
         *out = pbccs_map_stats{s.jobs, s.cells, s.launches, s.strips, s.deviceMs};
         if (reset && eng->mapper) eng->mapper->stats = map::MapStats();
+        return PBCCS_OK;
+    });
+}
+
+// ---- consensus kinetics (kinetics_kernels.hpp) -------------------------------------------------------------
+namespace {
+// ConsensusCore Sequence.cpp:44-105 (ComplementArray; note N <-> M), as k_map_fill's complement()
+char kin_complement(char c)
+{
+    switch (c) {
+        case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
+        case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a';
+        case 'N': return 'M'; case 'M': return 'N'; case 'n': return 'm'; case 'm': return 'n';
+        case '-': return '-';
+    }
+    return 127;
+}
+
+void kin_outputs(const std::vector<kinetics::ZmwOut>& zo, int n, pbccs_kinetics_output* out)
+{
+    for (int z = 0; z < n; ++z) {
+        out[z].n_contributed[0] = zo[z].contributed[0];
+        out[z].n_contributed[1] = zo[z].contributed[1];
+    }
+}
+
+kinetics::ZmwOut kin_out_view(const pbccs_kinetics_output& o)
+{
+    kinetics::ZmwOut v;
+    for (int k = 0; k < 4; ++k) {
+        v.mean[k] = o.mean[k];
+        v.code[k] = o.code[k];
+        v.coverage[k] = o.coverage[k];
+    }
+    v.contributed[0] = v.contributed[1] = 0;
+    v.readStatus = o.read_status;
+    return v;
+}
+}  // namespace
+
+void pbccs_kinetics_options_default(pbccs_kinetics_options* o)
+{
+    if (!o) return;
+    o->band.mode = PBCCS_BAND_OFF;
+    o->band.w = 0;
+}
+
+int pbccs_kinetics_pileup(pbccs_engine* eng, const pbccs_kinetics_pileup_input* in, int n, pbccs_kinetics_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    for (int z = 0; z < n; ++z)
+        if (in[z].consensus_len < 0 || in[z].n_reads < 0 || (in[z].n_reads > 0 && !in[z].reads))
+            return fail(PBCCS_EINVAL, "bad pbccs_kinetics_pileup_input");
+    return guarded([&] {
+        std::vector<std::vector<kinetics::ReadView>> rv((size_t)n);
+        std::vector<kinetics::ZmwView> zv((size_t)n);
+        std::vector<kinetics::ZmwOut> zo((size_t)n);
+        for (int z = 0; z < n; ++z) {
+            rv[z].resize((size_t)in[z].n_reads);
+            for (int k = 0; k < in[z].n_reads; ++k) {
+                const pbccs_kinetics_read& r = in[z].reads[k];
+                rv[z][k] = kinetics::ReadView{r.transcript, r.transcript_len, r.rc, r.rb, r.tb, r.te,
+                                              r.len,        r.ip,             r.pw, kinetics::kUsed};
+            }
+            zv[z] = kinetics::ZmwView{in[z].consensus_len, rv[z].data(), in[z].n_reads};
+            zo[z] = kin_out_view(out[z]);
+        }
+        {
+            std::lock_guard<std::mutex> lk(eng->kineticsMu);
+            eng->Kinetics().Run(zv.data(), n, zo.data());   // vets every read before any device work
+        }
+        kin_outputs(zo, n, out);
+        return PBCCS_OK;
+    });
+}
+
+namespace {
+// One slice of pbccs_kinetics_batch: ZMWs [z0, z1)
+void kinetics_slice(pbccs_engine* eng, const pbccs_kinetics_input* in, int z0, int z1,
+                    const pbccs_kinetics_options& opts, pbccs_kinetics_output* out)
+{
+    const int n = z1 - z0;
+    std::vector<map::MapGroup> groups((size_t)n);
+    for (int g = 0; g < n; ++g) {
+        const pbccs_kinetics_input& m = in[z0 + g];
+        groups[g] = map::MapGroup{m.consensus, m.consensus_len, m.seqs, m.lens, m.n_reads};
+    }
+    std::vector<map::MapResult> placed;
+    {
+        std::lock_guard<std::mutex> lk(eng->mapMu);
+        eng->Map().Run(groups.data(), n, 0.0f, &placed);
+    }
+    // the pairs: consensus[tb, te) against the oriented read's [rb, re)
+    std::vector<std::vector<kinetics::ReadView>> rv((size_t)n);
+    std::vector<std::string> oriented;   // the reverse-complemented extents (the forward ones are views)
+    std::vector<align::PairView> pairs;
+    std::vector<std::pair<int, int>> pairOf;   // (ZMW of the slice, read)
+    size_t idx = 0, nRev = 0;
+    for (int g = 0; g < n; ++g)
+        for (int r = 0; r < in[z0 + g].n_reads; ++r, ++idx)
+            if (placed[idx].mapped && placed[idx].rc) ++nRev;
+    oriented.reserve(nRev);   // the pairs keep pointers into the strings
+    idx = 0;
+    for (int g = 0; g < n; ++g) {
+        const pbccs_kinetics_input& m = in[z0 + g];
+        rv[g].resize((size_t)m.n_reads);
+        for (int r = 0; r < m.n_reads; ++r, ++idx) {
+            const map::MapResult& p = placed[idx];
+            kinetics::ReadView& v = rv[g][r];
+            v = kinetics::ReadView{nullptr, 0, p.rc, p.ext[0], p.ext[2], p.ext[3], m.lens[r], m.ip ? m.ip[r] : nullptr,
+                                   m.pw ? m.pw[r] : nullptr, kinetics::kUsed};
+            const int rb = p.ext[0], re = p.ext[1], tb = p.ext[2], te = p.ext[3];
+            if (!p.mapped) {
+                v.skip = kinetics::kUnmapped;
+                continue;
+            }
+            if (re <= rb || te <= tb) {
+                v.skip = kinetics::kEmptyExtent;
+                continue;
+            }
+            const char* q = m.seqs[r] + rb;
+            if (p.rc) {
+                std::string s((size_t)(re - rb), ' ');
+                const int I = m.lens[r];
+                for (int k = rb; k < re; ++k) s[(size_t)(k - rb)] = kin_complement(m.seqs[r][I - 1 - k]);
+                oriented.push_back(std::move(s));
+                q = oriented.back().data();
+            }
+            pairs.push_back(align::PairView{m.consensus + tb, te - tb, q, re - rb});
+            pairOf.emplace_back(g, r);
+        }
+    }
+    const int np = (int)pairs.size();
+    std::vector<align::PairResult> res((size_t)np);
+    if (np) {
+        const align::AlignScoring sc{PBCCS_ALIGN_NW, 0, -1, -1, -1, 0.f, 0.f, 0.f, 0.f, 0.f};   // AlignConfig::Default()
+        std::lock_guard<std::mutex> lk(eng->alignMu);
+        if (opts.band.mode != PBCCS_BAND_OFF) {
+            align::BandOptions bo;
+            bo.on = true;
+            bo.w = opts.band.mode == PBCCS_BAND_WIDTH ? opts.band.w : -1;
+            eng->Align().RunBanded(sc, pairs.data(), np, res.data(), bo, nullptr);
+        } else {
+            eng->Align().Run(sc, pairs.data(), np, res.data());
+        }
+    }
+    for (int k = 0; k < np; ++k) {
+        kinetics::ReadView& v = rv[pairOf[k].first][pairOf[k].second];
+        if (res[k].status != PBCCS_OK) {
+            v.skip = kinetics::kAlignFailed;
+            continue;
+        }
+        v.tr = res[k].transcript.data();
+        v.trLen = (int)res[k].transcript.size();
+    }
+    std::vector<kinetics::ZmwView> zv((size_t)n);
+    std::vector<kinetics::ZmwOut> zo((size_t)n);
+    for (int g = 0; g < n; ++g) {
+        zv[g] = kinetics::ZmwView{in[z0 + g].consensus_len, rv[g].data(), in[z0 + g].n_reads};
+        zo[g] = kin_out_view(out[z0 + g]);
+    }
+    {
+        std::lock_guard<std::mutex> lk(eng->kineticsMu);
+        eng->Kinetics().Run(zv.data(), n, zo.data());
+    }
+    kin_outputs(zo, n, out + z0);
+}
+}  // namespace
+
+int pbccs_kinetics_batch(pbccs_engine* eng, const pbccs_kinetics_input* in, int n, const pbccs_kinetics_options* opts,
+                         pbccs_kinetics_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    pbccs_kinetics_options o;
+    pbccs_kinetics_options_default(&o);
+    if (opts) o = *opts;
+    if (o.band.mode != PBCCS_BAND_OFF && o.band.mode != PBCCS_BAND_AUTO && o.band.mode != PBCCS_BAND_WIDTH)
+        return fail(PBCCS_EINVAL, "unknown band mode");
+    if (o.band.mode == PBCCS_BAND_WIDTH && o.band.w < 0) return fail(PBCCS_EINVAL, "negative band half-width");
+    for (int g = 0; g < n; ++g) {
+        const pbccs_kinetics_input& m = in[g];
+        if (!m.consensus || m.consensus_len <= 0) return fail(PBCCS_EINVAL, "empty consensus");
+        if (m.n_reads < 0 || (m.n_reads > 0 && (!m.seqs || !m.lens)))
+            return fail(PBCCS_EINVAL, "bad pbccs_kinetics_input");
+        if (m.consensus_len > map::kMaxLen) return fail(PBCCS_EINVAL, "consensus longer than 65535");
+        for (int r = 0; r < m.n_reads; ++r) {
+            if (m.lens[r] < 0 || (m.lens[r] > 0 && !m.seqs[r]))
+                return fail(PBCCS_EINVAL, "bad read (NULL sequence or negative length)");
+            if (m.lens[r] > map::kMaxLen) return fail(PBCCS_EINVAL, "read longer than 65535");
+        }
+    }
+    return guarded([&] {
+        // slices of at most kSliceBases read bases bound the host copies and the device pools of one pass
+        constexpr long long kSliceBases = 32LL << 20;
+        int z0 = 0;
+        while (z0 < n) {
+            long long bases = 0;
+            int z1 = z0;
+            while (z1 < n) {
+                long long b = 0;
+                for (int r = 0; r < in[z1].n_reads; ++r) b += in[z1].lens[r];
+                if (z1 > z0 && bases + b > kSliceBases) break;
+                bases += b;
+                ++z1;
+            }
+            kinetics_slice(eng, in, z0, z1, o, out);
+            z0 = z1;
+        }
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_kinetics_stats_get(pbccs_engine* eng, pbccs_kinetics_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->kineticsMu);
+        const kinetics::KinStats s = eng->kineticsRunner ? eng->kineticsRunner->stats : kinetics::KinStats();
+        *out = pbccs_kinetics_stats{s.reads,     s.unmapped, s.emptyExtent, s.alignFailed, s.columns,
+                                    s.positions, s.launches, s.columnsMs,   s.reduceMs};
+        if (reset && eng->kineticsRunner) eng->kineticsRunner->stats = kinetics::KinStats();
         return PBCCS_OK;
     });
 }

@@ -185,7 +185,7 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
-              polish_window=None, rich_qvs=False):
+              polish_window=None, rich_qvs=False, kinetics=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -204,6 +204,11 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     "fallback" (polish.WINDOW_FALLBACK names the codes).
     rich_qvs (pbccs_ccs_batch_ex4): the results also carry sub_qv, ins_qv, del_qv, sub_tag and ins_tag, the per-base
     rich QVs of the consensus (pbccs_amd.richqv), as polish_zmws(..., rich_qvs=True) gives them.
+    kinetics (pbccs_kinetics_batch, after the native call): every ZMW that ended Success or PoorQuality also
+    carries the consensus kinetics of pbccs_amd.kinetics -- fwd_ipd, fwd_pw, rev_ipd, rev_pw
+    (CodecV1 codes), the same names with _mean and _cov, fn and rn -- from its final consensus and those subreads,
+    whole and with their "ip" / "pw" tracks, whose add_read_results entry is SUCCESS.  A chunk whose reads carry
+    no tracks raises before any device work.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -214,6 +219,10 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     from . import lib as L
     from .polish import ConsensusSettings
     from .quiver import _struct_dtype
+    if kinetics:   # before any engine is touched
+        for z, c in enumerate(chunks):
+            if c["reads"] and not any(r.get("ip") is not None or r.get("pw") is not None for r in c["reads"]):
+                raise ValueError(f"ccs_batch(kinetics=True): the reads of chunk {z} carry no ip / pw tracks")
     eng = engine or default_engine()
     settings = settings or ConsensusSettings()
     n = len(chunks)
@@ -346,4 +355,14 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
             res[-1].update(sub_qv=rich_qv[0, c:c + rl].tolist(), ins_qv=rich_qv[1, c:c + rl].tolist(),
                            del_qv=rich_qv[2, c:c + rl].tolist(), sub_tag=rich_tag[0, c:c + rl].tobytes().decode(),
                            ins_tag=rich_tag[1, c:c + rl].tobytes().decode())
+    if kinetics:
+        from .kinetics import kinetics_batch
+        todo = [z for z in range(n) if res[z]["status_code"] in (0, 6) and res[z]["consensus"]]
+        got = kinetics_batch([(res[z]["consensus"],
+                               [{"seq": r["seq"], "ip": r.get("ip"), "pw": r.get("pw")}
+                                for r, a in zip(chunks[z]["reads"], res[z]["add_read_results"]) if a == 0])
+                              for z in todo], engine=eng)
+        for z, g in zip(todo, got):
+            g.pop("read_status")
+            res[z].update(g)
     return res

@@ -280,6 +280,40 @@ class CPolishExtras(ctypes.Structure):
                 ("repeat_applied", ctypes.POINTER(ctypes.c_longlong)), ("rich", ctypes.POINTER(CRichQvs))]
 
 
+class CKineticsRead(ctypes.Structure):
+    _fields_ = [("transcript", ctypes.c_char_p), ("transcript_len", ctypes.c_int), ("rc", ctypes.c_int),
+                ("rb", ctypes.c_int), ("tb", ctypes.c_int), ("te", ctypes.c_int), ("len", ctypes.c_int),
+                ("ip", ctypes.POINTER(ctypes.c_ushort)), ("pw", ctypes.POINTER(ctypes.c_ushort))]
+
+
+class CKineticsPileupInput(ctypes.Structure):
+    _fields_ = [("consensus_len", ctypes.c_int), ("n_reads", ctypes.c_int), ("reads", ctypes.POINTER(CKineticsRead))]
+
+
+class CKineticsOutput(ctypes.Structure):
+    _fields_ = [("mean", ctypes.POINTER(ctypes.c_ushort) * 4), ("code", ctypes.POINTER(ctypes.c_ubyte) * 4),
+                ("coverage", ctypes.POINTER(ctypes.c_int) * 4), ("n_contributed", ctypes.c_int * 2),
+                ("read_status", ctypes.POINTER(ctypes.c_int))]
+
+
+class CKineticsInput(ctypes.Structure):
+    _fields_ = [("consensus", ctypes.c_char_p), ("consensus_len", ctypes.c_int), ("n_reads", ctypes.c_int),
+                ("seqs", ctypes.POINTER(ctypes.c_char_p)), ("lens", ctypes.POINTER(ctypes.c_int)),
+                ("ip", ctypes.POINTER(ctypes.POINTER(ctypes.c_ushort))),
+                ("pw", ctypes.POINTER(ctypes.POINTER(ctypes.c_ushort)))]
+
+
+class CKineticsOptions(ctypes.Structure):
+    _fields_ = [("band", CAlignBand)]
+
+
+class CKineticsStats(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_longlong), ("skipped_unmapped", ctypes.c_longlong),
+                ("skipped_empty_extent", ctypes.c_longlong), ("skipped_align_failed", ctypes.c_longlong),
+                ("columns", ctypes.c_longlong), ("positions", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("columns_ms", ctypes.c_double), ("reduce_ms", ctypes.c_double)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -438,6 +472,12 @@ SIGNATURES = {
     "pbccs_polish_windowed_ex": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
                                      ctypes.POINTER(CWindowOptions), ctypes.POINTER(CPolishExtras),
                                      ctypes.POINTER(CZmwOutput), ctypes.POINTER(CWindowInfo)]),
+    # consensus kinetics
+    "pbccs_kinetics_options_default": (None, [ctypes.POINTER(CKineticsOptions)]),
+    "pbccs_kinetics_pileup": (I, [P, ctypes.POINTER(CKineticsPileupInput), I, ctypes.POINTER(CKineticsOutput)]),
+    "pbccs_kinetics_batch": (I, [P, ctypes.POINTER(CKineticsInput), I, ctypes.POINTER(CKineticsOptions),
+                                 ctypes.POINTER(CKineticsOutput)]),
+    "pbccs_kinetics_stats_get": (I, [P, ctypes.POINTER(CKineticsStats), I]),
 }
 # bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
 DIGIT_SIGNATURES = {
