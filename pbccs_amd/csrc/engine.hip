@@ -1041,8 +1041,12 @@ void ArrowBatch::FillReads(const std::vector<int>& readsIn)
         return q;
     };
     Relayout(readsIn);
+    // PBCCS_FILL_FIRST_PATH (test hook, read per batch): the path a read starts on -- 1: 16 lanes, 2: 64 lanes (LDS),
+    // 3: hybrid -- so that short reads run through the tall kernels too
+    const int firstPath = std::min(std::max(env_int("PBCCS_FILL_FIRST_PATH", 1), 1), 3);
     std::vector<int> todo[kPaths], serial, done;
     for (int r : readsIn) {
+        if (reads_[r].fillPath < firstPath) reads_[r].fillPath = firstPath;
         const int p = reads_[r].fillPath;
         if (p >= kPaths) serial.push_back(r);
         else todo[p].push_back(r);
@@ -1057,7 +1061,7 @@ void ArrowBatch::FillReads(const std::vector<int>& readsIn)
     // Tall paths: one read per wavefront, rows per lane PBCCS_TALL_ROWS (1 / 2, A/B; 4 measured slowest in every
     // A/B, profiles/r4c_tall_rows_ab.txt, and was removed); a column buffer holds whole chunks of 64 x rows rows.
     constexpr int tallG = 64;
-    static const int tallRows = env_int("PBCCS_TALL_ROWS", kTallRowsPerLane) == 1 ? 1 : 2;
+    const int tallRows = env_int("PBCCS_TALL_ROWS", kTallRowsPerLane) == 1 ? 1 : 2;   // (read per batch)
     const long long chunk = (long long)tallG * tallRows;
     const long long tallGroupLds = (long long)kCoopLdsBytes;
     auto full_rows = [&](int maxI) { return ((long long)maxI + chunk) / chunk * chunk; };   // >= I + 1 rows
@@ -1079,8 +1083,8 @@ void ArrowBatch::FillReads(const std::vector<int>& readsIn)
         }
         // hybrid: as many LDS rows as fit, up to kHybridRows (the rest of a column goes to global memory)
         // PBCCS_HYBRID_LDS_KB / PBCCS_HYBRID_ROWS (A/B): the hybrid path's LDS budget per read and its row cap
-        static const long long hybLds = (long long)env_int("PBCCS_HYBRID_LDS_KB", (int)(kCoopLdsBytes >> 10)) << 10;
-        static const long long hybRows = env_int("PBCCS_HYBRID_ROWS", kHybridRows);
+        const long long hybLds = (long long)env_int("PBCCS_HYBRID_LDS_KB", (int)(kCoopLdsBytes >> 10)) << 10;
+        const long long hybRows = env_int("PBCCS_HYBRID_ROWS", kHybridRows);
         const long long hroom = (std::min<long long>(hybLds, 160 << 10) - (long long)coop_group_bytes(0, w, 0)) / 16 / 64 * 64;
         const long long want = std::min(std::min(full, hroom), hybRows);
         return want >= 64 ? (int)want : 0;

@@ -65,6 +65,14 @@ struct Task {
     long long* gB;
     long long* gCap;
 
+    // a group-uniform value.  One read per wavefront: moved to a scalar register, so what is computed from it runs on
+    // the scalar unit (the compiler cannot prove the band's bounds uniform and would keep them per lane)
+    __device__ __forceinline__ int uni(int x) const
+    {
+        if constexpr (G == 64) return __builtin_amdgcn_readfirstlane(x);
+        return x;
+    }
+
     // buffer b (0 / 1), row k (no runtime-indexed pointer arrays: they would live in scratch).  The hybrid
     // path selects an LDS or global address per lane and accesses it through one generic (flat) pointer.
     // (buffer 1 follows buffer 0 in both places: offsets, not a selected pointer member, keep T in registers)
@@ -72,15 +80,49 @@ struct Task {
     // k / 2).  A lane's rows are k0 + 2 lane + r with k0 + r of one parity across the group, so every LDS access
     // of the group lands in one plane at consecutive doubles -- no bank conflicts (a 16-byte lane stride into one
     // linear buffer put two lanes on each bank: 27% of the tall fill's LDS cycles, profiles/r4h2_pmc_summary.txt).
-    bool split;
-    __device__ __forceinline__ int lrow(int k) const { return split ? (k & 1) * (hcap >> 1) + (k >> 1) : k; }
+    template <int R>
+    __device__ __forceinline__ int lrow(int k) const
+    {
+        static_assert(R <= 2, "the split layout has two planes");
+        return R > 1 ? (k & 1) * (hcap >> 1) + (k >> 1) : k;
+    }
+    template <int R>
     __device__ __forceinline__ double* cptr(int b, int k) const
     {
-        if (!gcol) return lds0 + (b ? hcap : 0) + lrow(k);
-        return k < hcap ? lds0 + (b ? hcap : 0) + lrow(k) : glob0 + (b ? glob1 - glob0 : 0) + (k - hcap);
+        if (!gcol) return lds0 + (b ? hcap : 0) + lrow<R>(k);
+        return k < hcap ? lds0 + (b ? hcap : 0) + lrow<R>(k) : glob0 + (b ? glob1 - glob0 : 0) + (k - hcap);
     }
-    __device__ __forceinline__ double cget(int b, int k) const { return *cptr(b, k); }
-    __device__ __forceinline__ void cset(int b, int k, double v) const { *cptr(b, k) = v; }
+    template <int R>
+    __device__ __forceinline__ double cget(int b, int k) const { return *cptr<R>(b, k); }
+    template <int R>
+    __device__ __forceinline__ void cset(int b, int k, double v) const { *cptr<R>(b, k) = v; }
+    // LDS-only paths (not the hybrid one).  Row (c G + lane) R + r of buffer b, a lane's row r of chunk c: plane r
+    // at c G + lane, so a chunk's addresses are a per-lane base plus constants.
+    template <int R>
+    __device__ __forceinline__ double* lptr(int b, int c, int r) const
+    {
+        static_assert(R <= 2, "the split layout has two planes");
+        return lds0 + (b ? hcap : 0) + (R > 1 ? r * (hcap >> 1) : 0) + c * G + g.lane;
+    }
+    // Row k = s + R lane of buffer b when 0 <= k < h (h <= hcap), else 0.0; s is group-uniform.  One unconditional
+    // load from a clamped address inside the buffer and a select: no load waits inside a predicated region, and a
+    // stale in-buffer value is discarded.  R = 2: k's parity -- the plane -- is s's, group-uniform, and the index
+    // in the plane is (s >> 1) + lane.
+    template <int R>
+    __device__ __forceinline__ double lget_sel(int b, int s, int h) const
+    {
+        static_assert(R <= 2, "the split layout has two planes");
+        const bool in = (unsigned)(s + R * g.lane) < (unsigned)h;
+        double v;
+        if constexpr (R > 1) {
+            const int half = hcap >> 1;
+            const int p = min(max((s >> 1) + g.lane, 0), half - 1);
+            v = lds0[(b ? hcap : 0) + (s & 1) * half + p];
+        } else {
+            v = lds0[(b ? hcap : 0) + min(max(s + g.lane, 0), hcap - 1)];
+        }
+        return in ? v : 0.0;
+    }
     // template window base idx (nibble code; past the window or the template: kBaseOther) and its context slot
     __device__ __forceinline__ int TBase(int idx) const
     {
@@ -94,6 +136,28 @@ struct Task {
     __device__ __forceinline__ int RB(int x) const
     {
         return nib(rdW, x);
+    }
+    // read bases x0 .. x0 + R - 1, code 15 ("no base") outside [0, I): the words that hold them are loaded once from
+    // a clamped position and the codes shifted out -- no branch, one LDS round trip.  (The word after the read's
+    // last is inside the slot: the template's words follow.)
+    template <int R>
+    __device__ __forceinline__ void RBs(int x0, int (&rb)[R]) const
+    {
+        static_assert(R <= 9, "R codes from a clamped position span at most two words");
+        const int xc = min(max(x0, 0), I - 1);
+        if constexpr (R == 1) {
+            const int v = nib(rdW, xc);
+            rb[0] = (unsigned)x0 < (unsigned)I ? v : 15;
+        } else {
+            const int w = xc >> 3;
+            const unsigned long long bits = (unsigned long long)rdW[w] | ((unsigned long long)rdW[w + 1] << 32);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int x = x0 + r;   // a valid x lies in [8 w, 8 w + 16)
+                const int v = (int)(bits >> (((x - 8 * w) & 15) << 2)) & 15;
+                rb[r] = (unsigned)x < (unsigned)I ? v : 15;
+            }
+        }
     }
 };
 
@@ -143,10 +207,11 @@ __device__ __forceinline__ void col_fence(bool gcol)
 // threshold.  `amb` flags that case (and a pm too small for the bound); the caller divides there.
 __device__ __forceinline__ bool thr_ge(double x, double pm, double lo, double hi, bool& amb)
 {
+    // (no short circuit: both products and every comparison unconditionally, straight-line code)
     const bool ge = x >= pm * hi;
     const bool lt = x < pm * lo;
-    amb = pm != 0.0 && (pm < 0x1p-960 || (!ge && !lt));
-    return ge || pm == 0.0;
+    amb = (pm != 0.0) & ((pm < 0x1p-960) | (!ge & !lt));
+    return ge | (pm == 0.0);
 }
 
 // ---- the certified fast path (SCAN) ------------------------------------------------
@@ -162,14 +227,15 @@ __device__ __forceinline__ bool thr_ge(double x, double pm, double lo, double hi
 // (kFillUncertain).
 __device__ __forceinline__ double scan_col_dev(double D, int chunks, int rowsPerChunk)
 {
-    return D + (4.0 * (double)chunks * (double)rowsPerChunk + 40.0 * (double)chunks + 8.0) * kUnitRoundoff;
+    // (the count is a small integer, exact in double however it is summed: one conversion)
+    return D + (double)(4 * chunks * rowsPerChunk + 40 * chunks + 8) * kUnitRoundoff;
 }
 // Exact zeros are exact on both paths (a cell is 0 only when every term reaching it is, whatever the association),
 // so 0 against a 0 threshold (the running maximum of leading zero rows) is the reference's decision, not an uncertain one.
 __device__ __forceinline__ bool near_thr(double x, double t, double margin)
 {
     const double mx = fmax(x, t);
-    return mx > 0.0 && fabs(x - t) <= margin * mx;
+    return (mx > 0.0) & (fabs(x - t) <= margin * mx);
 }
 
 // ---- band growth ---------------------------------------------------------------------------------
@@ -278,7 +344,7 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
         a.L(0) = 0.0;
     }
     int prev = 0, cur = 1;   // column buffers
-    if (lane == 0) T.cset(prev, 0, 1.0);
+    if (lane == 0) T.template cset<R>(prev, 0, 1.0);
     int pb = 0, pe = 1;
     double D = 0.0;     // SCAN: the pass's relative deviation bound so far (scan_col_dev)
     int unc = 0;   // SCAN: the uncertain decisions met (PassOut::unc)
@@ -326,14 +392,18 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
         if (selfValid) {
             if (sx < sy) { hb = min(sx, hb); he = max(sy, he); }
         }
-        const int reqEnd = min(I, he);
+        const int reqEnd = T.uni(min(I, he));
         const int nextBase = tA, nextCtx = (T.start + j + 1 < T.L) ? ctx_code(tA, tB) : kCtxZero;   // TBase / TCtx(j)
         const int tC = T.TBase(j + 2);   // for the next column
         const double* cp = T.ctx + curCtx * kCtxStride;
         const double* pp = T.ctx + prevCtx * kCtxStride;
         const double pMatch = pp[kM], pDel = pp[kD];
         const double cBranch = cp[kB], cStick3 = cp[kS3];
-        const int b = hb;
+        // the column's factors of the match and deletion moves: a match into column 1 is taken from row 1 only and as
+        // it is (x 1.0 is exact), elsewhere from every row but 1 with pMatch; no deletion into column 1 (a value
+        // x 0.0 is the +0.0 of the select it replaces: the values are finite and non-negative)
+        const double mFac = (j == 1) ? 1.0 : pMatch, dFac = (j > 1) ? pDel : 0.0;
+        const int b = T.uni(hb);
         double mx = 0.0, aLast[R];
         int e = b, nc = 0;
         if (b < I) {
@@ -341,15 +411,25 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
             // the previous column's rows of a chunk: diag and left of the lane's rows (ibx - 1 .. ibx + R - 1).  GC (the
             // hybrid path, rows past the LDS buffer in global memory): loaded one chunk ahead into pvN, so a global
             // row's latency overlaps the chunk before it (the loads precede the chunk's stores to the other buffer)
-            auto load_prev = [&](int ibx, double (&dst)[R + 1]) {
+            // (i0x: the chunk's first row.  The 64-lane LDS-only kernels: unconditional loads and a select,
+            // Task::lget_sel.  The hybrid path keeps the guard -- a clamped row could leave the group's slot of
+            // colScratch -- and so does the 16-lane kernel, where the select form measured more VALU per cell: its
+            // four reads per wavefront leave nothing uniform to hoist)
+            const int hPrev = T.uni(pe - pb);
+            auto load_prev = [&](int i0x, double (&dst)[R + 1]) {
+                const int s0 = T.uni(i0x - 1 - pb);
 #pragma unroll
                 for (int q = 0; q <= R; ++q) {
-                    const int row = ibx - 1 + q;
-                    dst[q] = (row >= pb && row < pe) ? T.cget(prev, row - pb) : 0.0;
+                    if constexpr (GC || G < 64) {
+                        const int row = i0x + lane * R - 1 + q;
+                        dst[q] = (row >= pb && row < pe) ? T.template cget<R>(prev, row - pb) : 0.0;
+                    } else {
+                        dst[q] = T.template lget_sel<R>(prev, s0 + q, hPrev);
+                    }
                 }
             };
             double pvN[R + 1];
-            if constexpr (PF) load_prev(b + lane * R, pvN);
+            if constexpr (PF) load_prev(b, pvN);
             for (int i0 = b;; i0 += CH) {
                 if ((nc + 1) * CH > T.rowsCap) {
                     out.tall = true;
@@ -365,18 +445,20 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                     if constexpr (PF) {
 #pragma unroll
                         for (int q = 0; q <= R; ++q) pv[q] = pvN[q];
-                        load_prev(ib + CH, pvN);
+                        load_prev(i0 + CH, pvN);
                     } else {
-                        load_prev(ib, pv);
+                        load_prev(i0, pv);
                     }
+                    int rbs[R];   // read bases of rows ib .. ib + R - 1 (15: no such row)
+                    T.template RBs<R>(ib - 1, rbs);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const int i = ib + r;
-                        const int rb = (i >= 1 && i <= I) ? T.RB(i - 1) : 15;
+                        const int rb = rbs[r];
                         const double mpe = pv[r] * (rb == curBase ? T.prNot : T.prThird);
-                        m[r] = (i == 1 && j == 1) ? mpe : ((i != 1 && j != 1) ? mpe * pMatch : 0.0);
+                        m[r] = mpe * (((i == 1) == (j == 1)) ? mFac : 0.0);
                         k[r] = (i > 1) ? (rb == nextBase ? cBranch : cStick3) : 0.0;
-                        d[r] = (j > 1) ? pv[r + 1] * pDel : 0.0;
+                        d[r] = pv[r + 1] * dFac;
                         x[r] = 0.0;
                     }
                 }
@@ -441,26 +523,33 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                         pmR[r] = run;
                     }
                 }
-                bool ge[R], amb = false;   // x >= pm / sdn where the test is read (rows past reqEnd - 1)
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int i = ib + r;
-                    bool a;
-                    ge[r] = thr_ge(x[r], pmR[r], T.sdnInvLow, T.sdnInvHigh, a);
-                    amb = amb || (a && i + 1 < I && i + 1 >= reqEnd);
-                }
-                if (__ballot(amb) != 0) {   // rare: the quotient itself
-#pragma unroll
-                    for (int r = 0; r < R; ++r) ge[r] = x[r] >= pmR[r] / T.sdn;
-                }
+                // A chunk that ends before reqEnd (<= I) reads no test and stops nowhere: every row continues.  One
+                // read per wavefront: a wave-uniform branch around the tests (several reads per wavefront: a lane mask,
+                // not taken)
+                const bool tests = G < 64 || i0 + CH >= reqEnd;
                 int fs = R;   // the lane's first row where the loop stops
+                unsigned long long stop = 0;
+                if (tests) {
+                    bool ge[R], amb = false;   // x >= pm / sdn where the test is read (rows past reqEnd - 1)
 #pragma unroll
-                for (int r = R - 1; r >= 0; --r) {
-                    const int i = ib + r;
-                    const bool cont = (i + 1 < I) && (ge[r] || i + 1 < reqEnd);
-                    if (!cont) fs = r;
+                    for (int r = 0; r < R; ++r) {
+                        const int i = ib + r;
+                        bool a;
+                        ge[r] = thr_ge(x[r], pmR[r], T.sdnInvLow, T.sdnInvHigh, a);
+                        amb = amb || (a && i + 1 < I && i + 1 >= reqEnd);
+                    }
+                    if (__ballot(amb) != 0) {   // rare: the quotient itself
+#pragma unroll
+                        for (int r = 0; r < R; ++r) ge[r] = x[r] >= pmR[r] / T.sdn;
+                    }
+#pragma unroll
+                    for (int r = R - 1; r >= 0; --r) {
+                        const int i = ib + r;
+                        const bool cont = (i + 1 < I) && (ge[r] || i + 1 < reqEnd);
+                        if (!cont) fs = r;
+                    }
+                    stop = T.g.bits(fs < R);
                 }
-                const unsigned long long stop = T.g.bits(fs < R);
                 const int lastLane = stop ? (__ffsll((long long)stop) - 1) : (G - 1);
                 double pmAt = pmR[R - 1];
 #pragma unroll
@@ -477,7 +566,7 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                         const int i = ib + r;
                         const bool matters = (i + 1 < I) && (i + 1 >= reqEnd);
                         const bool upto = !stop || lane < lastLane || (lane == lastLane && r <= rsStop);
-                        u = u || (matters && upto && near_thr(x[r], pmR[r] * T.sdnInv, mg));
+                        u = u | (matters & upto & near_thr(x[r], pmR[r] * T.sdnInv, mg));
                     }
                     if (T.g.bits(u) != 0) unc |= 1;
                 }
@@ -491,7 +580,10 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                     break;
                 }
 #pragma unroll
-                for (int r = 0; r < R; ++r) T.cset(cur, (nc - 1) * CH + lane * R + r, x[r]);
+                for (int r = 0; r < R; ++r) {
+                    if constexpr (GC) T.template cset<R>(cur, (nc - 1) * CH + lane * R + r, x[r]);
+                    else *T.template lptr<R>(cur, nc - 1, r) = x[r];
+                }
                 carry = T.g.bcast_last(x[R - 1]);
             }
         }
@@ -507,12 +599,22 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
         const bool scale = (mx != 0.0 && mx != 1.0);
         int nhb = e;
         bool found = false;
-        const double mh = SCAN ? T.devScale * (3.0 * scan_col_dev(D, nc, CH) + 4.0 * kUnitRoundoff) : 0.0;   // hint margin
+        const double Dc = SCAN ? scan_col_dev(D, nc, CH) : 0.0;
+        const double mh = SCAN ? T.devScale * (3.0 * Dc + 4.0 * kUnitRoundoff) : 0.0;   // hint margin
+        // the band's room from this column's first value, once per column (stored + kk < a.cap per row otherwise)
+        const int capRows = (int)max(0LL, min((long long)0x7fffffff, a.cap - stored));
         // two chunks per iteration: their divisions and LDS round trips overlap (tall columns have many chunks)
         // GC: the next chunk's values are loaded before this chunk's stores (its global rows' latency overlaps)
         auto load_cur = [&](int cx, double (&dst)[R]) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) dst[r] = (cx == nc - 1) ? aLast[r] : T.cget(cur, cx * CH + lane * R + r);
+            for (int r = 0; r < R; ++r) {
+                if constexpr (GC) {
+                    dst[r] = (cx == nc - 1) ? aLast[r] : T.template cget<R>(cur, cx * CH + lane * R + r);
+                } else {   // the chunk is inside the buffer (cx < nc): a plain load, the last chunk's discarded
+                    const double ld = *T.template lptr<R>(cur, cx, r);
+                    dst[r] = (cx == nc - 1) ? aLast[r] : ld;
+                }
+            }
         };
         double xN[R];
         if constexpr (PFS) load_cur(0, xN);
@@ -535,8 +637,9 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                 const double x = xc[r];
                 const double v = scale ? x / mx : x;
                 if (ok) {
-                    T.cset(cur, kk, v);
-                    if (store && stored + kk < a.cap) a.V(stored + kk) = v;
+                    if constexpr (GC) T.template cset<R>(cur, kk, v);
+                    else *T.template lptr<R>(cur, c, r) = v;
+                    if (store && kk < capRows) a.V(stored + kk) = v;
                 }
                 if (fh == R && ok && !(v < thrF)) fh = r;
                 vv[r] = ok ? v : -1.0;
@@ -549,7 +652,7 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                     bool u = false;
 #pragma unroll
                     for (int r = 0; r < R; ++r)
-                        u = u || (vv[r] >= 0.0 && (lane < hl || (lane == hl && r <= fhl)) && near_thr(vv[r], thrF, mh));
+                        u = u | ((vv[r] >= 0.0) & ((lane < hl) | ((lane == hl) & (r <= fhl))) & near_thr(vv[r], thrF, mh));
                     if (T.g.bits(u) != 0) unc |= 2;
                 }
             }
@@ -559,7 +662,7 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
                 found = true;
             }
         }
-        if constexpr (SCAN) D = scan_col_dev(D, nc, CH) + kUnitRoundoff;   // the column's rows and its scale
+        if constexpr (SCAN) D = Dc + kUnitRoundoff;   // the column's rows and its scale
         if (!counting && stored + add > a.cap) ovf = true;
         out.changed = out.changed || b != sx || e != sy;
         out.maxH = max(out.maxH, e - b);
@@ -591,7 +694,7 @@ __device__ PassOut coop_alpha(const Task<G>& T, Band& a, Band& o, bool guided, b
     // pinned final match (:169-179)
     const double em = (T.RB(I - 1) == T.TBase(J - 1)) ? T.prNot : T.prThird;
     const bool lastIn = I - 1 >= pb && I - 1 < pe;
-    const double lik = (lastIn ? T.cget(prev, I - 1 - pb) : 0.0) * em;
+    const double lik = (lastIn ? T.template cget<R>(prev, I - 1 - pb) : 0.0) * em;
     const double c = (0.0 < lik) ? lik : 0.0;
     double v = lik, ls = 0.0;
     if (c != 0.0 && c != 1.0) { v = lik / c; ls = log(c); }
@@ -644,7 +747,7 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
     }
     // the next column (j + 1) holds rows [pb, pe) at index pe - 1 - row
     int nxt = 0, cur = 1;   // column buffers
-    if (lane == 0) T.cset(nxt, 0, 1.0);
+    if (lane == 0) T.template cset<R>(nxt, 0, 1.0);
     int pb = I, pe = I + 1;
     double D = 0.0;     // SCAN: the pass's relative deviation bound so far (scan_col_dev)
     int unc = 0;   // SCAN: the uncertain decisions met (PassOut::unc)
@@ -688,24 +791,33 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
         if (selfValid) {
             if (sx < sy) { hb = min(sx, hb); he = max(sy, he); }
         }
-        const int reqBegin = max(0, hb);
+        const int reqBegin = T.uni(max(0, hb));
         const double* cp = T.ctx + curCtx * kCtxStride;
         const double cMatch = cp[kM], cDel = cp[kD], cBranch = cp[kB], cStick3 = cp[kS3];
-        const int e = he;
+        const int e = T.uni(he);
+        // the column's deletion factor (see coop_alpha); the last row's match into column J - 1 is taken as it is
+        const double dFac = (j < J - 1 && j > 0) ? cDel : 0.0, mLast = (j == J - 1) ? 1.0 : 0.0;
         double mx = 0.0, aLast[R];
         int b = e, nc = 0;
         if (e - 1 > 0) {
             double carry = 0.0;
             // the next column's rows of a chunk (rows e - obx .. e - obx - R); GC: one chunk ahead (see coop_alpha)
-            auto load_next = [&](int obx, double (&dst)[R + 1]) {
+            // (o0x: the chunk's first offset; the select and the guarded form as coop_alpha's load_prev)
+            const int hNext = T.uni(pe - pb);
+            auto load_next = [&](int o0x, double (&dst)[R + 1]) {
+                const int s0 = T.uni(pe - 1 - e + o0x);
 #pragma unroll
                 for (int q = 0; q <= R; ++q) {
-                    const int row = e - obx - q;
-                    dst[q] = (row >= pb && row < pe) ? T.cget(nxt, pe - 1 - row) : 0.0;
+                    if constexpr (GC || G < 64) {
+                        const int row = e - (o0x + lane * R) - q;
+                        dst[q] = (row >= pb && row < pe) ? T.template cget<R>(nxt, pe - 1 - row) : 0.0;
+                    } else {
+                        dst[q] = T.template lget_sel<R>(nxt, s0 + q, hNext);
+                    }
                 }
             };
             double pvN[R + 1];
-            if constexpr (PF) load_next(lane * R, pvN);
+            if constexpr (PF) load_next(0, pvN);
             for (int c = 0;; ++c) {
                 if ((c + 1) * CH > T.rowsCap) {
                     out.tall = true;
@@ -721,19 +833,21 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                     if constexpr (PF) {
 #pragma unroll
                         for (int q = 0; q <= R; ++q) pv[q] = pvN[q];
-                        load_next(ob + CH, pvN);
+                        load_next((c + 1) * CH, pvN);
                     } else {
-                        load_next(ob, pv);
+                        load_next(c * CH, pv);
                     }
+                    int rbs[R];   // read bases of rows e - ob - R .. e - 1 - ob (15: no such row)
+                    T.template RBs<R>(e - ob - R, rbs);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const int i = e - 1 - ob - r;
-                        const int nb = (i >= 0 && i < I) ? T.RB(i) : 15;
+                        const int nb = rbs[R - 1 - r];
                         const bool same = nb == nextBase;
                         const double mpe = pv[r] * (same ? T.prNot : T.prThird);
-                        m[r] = (i < I - 1) ? mpe * cMatch : ((i == I - 1 && j == J - 1) ? mpe : 0.0);
+                        m[r] = mpe * (i < I - 1 ? cMatch : (i == I - 1 ? mLast : 0.0));
                         k[r] = (i < I - 1 && i > 0) ? (same ? cBranch : cStick3) : 0.0;
-                        d[r] = (j < J - 1 && j > 0) ? pv[r + 1] * cDel : 0.0;
+                        d[r] = pv[r + 1] * dFac;
                         x[r] = 0.0;
                     }
                 }
@@ -796,26 +910,31 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                         pmR[r] = run;
                     }
                 }
-                bool ge[R], amb = false;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int i = e - 1 - ob - r;
-                    bool a;
-                    ge[r] = thr_ge(x[r], pmR[r], T.sdnInvLow, T.sdnInvHigh, a);
-                    amb = amb || (a && i - 1 > 0 && i - 1 < reqBegin);
-                }
-                if (__ballot(amb) != 0) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) ge[r] = x[r] >= pmR[r] / T.sdn;
-                }
+                // a chunk whose lowest row lies above max(reqBegin, 1) reads no test and stops nowhere (see coop_alpha)
+                const bool tests = G < 64 || e - (c + 1) * CH - 1 < max(reqBegin, 1);
                 int fs = R;
+                unsigned long long stop = 0;
+                if (tests) {
+                    bool ge[R], amb = false;
 #pragma unroll
-                for (int r = R - 1; r >= 0; --r) {
-                    const int i = e - 1 - ob - r;
-                    const bool cont = (i - 1 > 0) && (ge[r] || i - 1 >= reqBegin);
-                    if (!cont) fs = r;
+                    for (int r = 0; r < R; ++r) {
+                        const int i = e - 1 - ob - r;
+                        bool a;
+                        ge[r] = thr_ge(x[r], pmR[r], T.sdnInvLow, T.sdnInvHigh, a);
+                        amb = amb || (a && i - 1 > 0 && i - 1 < reqBegin);
+                    }
+                    if (__ballot(amb) != 0) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) ge[r] = x[r] >= pmR[r] / T.sdn;
+                    }
+#pragma unroll
+                    for (int r = R - 1; r >= 0; --r) {
+                        const int i = e - 1 - ob - r;
+                        const bool cont = (i - 1 > 0) && (ge[r] || i - 1 >= reqBegin);
+                        if (!cont) fs = r;
+                    }
+                    stop = T.g.bits(fs < R);
                 }
-                const unsigned long long stop = T.g.bits(fs < R);
                 const int lastLane = stop ? (__ffsll((long long)stop) - 1) : (G - 1);
                 double pmAt = pmR[R - 1];
 #pragma unroll
@@ -831,7 +950,7 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                         const int i = e - 1 - ob - r;
                         const bool matters = (i - 1 > 0) && (i - 1 < reqBegin);
                         const bool upto = !stop || lane < lastLane || (lane == lastLane && r <= rsStop);
-                        u = u || (matters && upto && near_thr(x[r], pmR[r] * T.sdnInv, mg));
+                        u = u | (matters & upto & near_thr(x[r], pmR[r] * T.sdnInv, mg));
                     }
                     if (T.g.bits(u) != 0) unc |= 1;
                 }
@@ -845,7 +964,10 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                     break;
                 }
 #pragma unroll
-                for (int r = 0; r < R; ++r) T.cset(cur, ob + r, x[r]);
+                for (int r = 0; r < R; ++r) {
+                    if constexpr (GC) T.template cset<R>(cur, ob + r, x[r]);
+                    else *T.template lptr<R>(cur, c, r) = x[r];
+                }
                 carry = T.g.bcast_last(x[R - 1]);
             }
         }
@@ -860,10 +982,19 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
         const bool scale = (mx != 0.0 && mx != 1.0);
         int nhe = b;
         bool found = false;
-        const double mh = SCAN ? T.devScale * (3.0 * scan_col_dev(D, nc, CH) + 4.0 * kUnitRoundoff) : 0.0;   // hint margin
+        const double Dc = SCAN ? scan_col_dev(D, nc, CH) : 0.0;
+        const double mh = SCAN ? T.devScale * (3.0 * Dc + 4.0 * kUnitRoundoff) : 0.0;   // hint margin
+        const int capRows = (int)max(0LL, min((long long)0x7fffffff, bm.cap - stored));   // as coop_alpha's
         auto load_cur = [&](int cx, double (&dst)[R]) {   // GC: one chunk ahead (see coop_alpha)
 #pragma unroll
-            for (int r = 0; r < R; ++r) dst[r] = (cx == nc - 1) ? aLast[r] : T.cget(cur, cx * CH + lane * R + r);
+            for (int r = 0; r < R; ++r) {
+                if constexpr (GC) {
+                    dst[r] = (cx == nc - 1) ? aLast[r] : T.template cget<R>(cur, cx * CH + lane * R + r);
+                } else {   // the chunk is inside the buffer (cx < nc): a plain load, the last chunk's discarded
+                    const double ld = *T.template lptr<R>(cur, cx, r);
+                    dst[r] = (cx == nc - 1) ? aLast[r] : ld;
+                }
+            }
         };
         double xN[R];
         if constexpr (PFS) load_cur(0, xN);
@@ -886,8 +1017,9 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                 const double x = xc[r];
                 const double v = scale ? x / mx : x;
                 if (ok) {
-                    T.cset(cur, off, v);
-                    if (store && stored + off < bm.cap) bm.V(stored + off) = v;
+                    if constexpr (GC) T.template cset<R>(cur, off, v);
+                    else *T.template lptr<R>(cur, c, r) = v;
+                    if (store && off < capRows) bm.V(stored + off) = v;
                 }
                 if (fh == R && ok && !(v < thrF)) fh = r;
                 vv[r] = ok ? v : -1.0;
@@ -900,7 +1032,7 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                     bool u = false;
 #pragma unroll
                     for (int r = 0; r < R; ++r)
-                        u = u || (vv[r] >= 0.0 && (lane < hl || (lane == hl && r <= fhl)) && near_thr(vv[r], thrF, mh));
+                        u = u | ((vv[r] >= 0.0) & ((lane < hl) | ((lane == hl) & (r <= fhl))) & near_thr(vv[r], thrF, mh));
                     if (T.g.bits(u) != 0) unc |= 2;
                 }
             }
@@ -910,7 +1042,7 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
                 found = true;
             }
         }
-        if constexpr (SCAN) D = scan_col_dev(D, nc, CH) + kUnitRoundoff;   // the column's rows and its scale
+        if constexpr (SCAN) D = Dc + kUnitRoundoff;   // the column's rows and its scale
         if (!counting && stored + add > bm.cap) ovf = true;
         out.changed = out.changed || b != sx || e != sy;
         out.maxH = max(out.maxH, e - b);
@@ -936,7 +1068,7 @@ __device__ PassOut coop_beta(const Task<G>& T, Band& bm, Band& o, bool guided, b
     }
     const double em = (T.TBase(0) == T.RB(0)) ? T.prNot : T.prThird;
     const bool lastIn = 1 >= pb && 1 < pe;
-    const double raw = em * (lastIn ? T.cget(nxt, pe - 2) : 0.0);
+    const double raw = em * (lastIn ? T.template cget<R>(nxt, pe - 2) : 0.0);
     const double c = (0.0 < raw) ? raw : 0.0;
     double v = raw, ls = 0.0;
     if (c != 0.0 && c != 1.0) { v = raw / c; ls = log(c); }
@@ -1035,8 +1167,8 @@ __device__ __forceinline__ void fill_read(const DevBatch& B, const CoopFill& F, 
     Task<G> T;
     T.g.lane = lane;
     T.g.base = (int)threadIdx.x & ~(G - 1);
-    T.I = I;
-    T.J = J;
+    T.I = T.uni(I);
+    T.J = T.uni(J);
     T.L = tv.L;
     T.start = tv.start;
     T.rdW = rdW;
@@ -1047,7 +1179,6 @@ __device__ __forceinline__ void fill_read(const DevBatch& B, const CoopFill& F, 
     T.glob0 = GC ? F.colScratch + (size_t)t * 2 * F.gRows : nullptr;
     T.glob1 = GC ? T.glob0 + F.gRows : nullptr;
     T.hcap = F.hcap;
-    T.split = R == 2;   // launch_fill_coop checks that hcap holds whole chunks (even)
     T.rowsCap = GC ? F.hcap + F.gRows : F.hcap;
     T.gcol = GC;
     T.chainExit = F.chainExit;
