@@ -1090,6 +1090,78 @@ int pbccs_ccs_batch_ex4(pbccs_engine* eng, const pbccs_ccs_input* in, int n, con
                         const pbccs_polish_options* opts, const pbccs_polish_extras* extras, pbccs_ccs_output* out,
                         pbccs_window_info* info);
 
+/* ---- directional consensus: strand-discordance screen and per-strand polish -----------
+ * Rules of this project's own: the reference declares ConsensusSettings::Directional and stops at a TODO
+ * (include/pacbio/ccs/Consensus.h:94-109).  For a single-base mutation m of the final template, sum_fwd / sum_rev
+ * are the sums of Scores(m, 0) over the active forward / reverse reads that score m, in AddRead order (plain FP64
+ * adds, no fast-score break), and n_fwd / n_rev count those reads.  m qualifies when n_fwd >= min_reads, n_rev >=
+ * min_reads and one sum lies above min_score while the other lies below -min_score (a NaN sum never qualifies).  A
+ * template position is a discordant site when one of its unique single-base mutations qualifies; it reports the
+ * qualifying mutation with the largest min(|sum_fwd|, |sum_rev|), the first in enumeration order on a tie.
+ * min_score defaults to 12.5, the magnitude of the reference's FastScoreThreshold, and min_reads to 2. */
+typedef struct {
+    double min_score;
+    int min_reads;
+    int min_sites;     /* directional == 1: a ZMW is split when it has at least this many sites (default 1) */
+    int directional;   /* 0: the screen only, 1: split the discordant ZMWs, 2: split every ZMW */
+} pbccs_strand_options;
+void pbccs_strand_options_default(pbccs_strand_options* o);
+
+/* One per ZMW.  The five site arrays are caller buffers of cap entries (type: PBCCS_INSERTION / DELETION /
+ * SUBSTITUTION; base '-' for a deletion); n_sites = the sites written, in template order, 0 for a ZMW that ends
+ * neither SUCCESS nor POOR_QUALITY, -required when cap is too small (nothing is written then and the call returns
+ * PBCCS_ERANGE after all outputs are written).  split: the ZMW was polished once more per strand; fwd / rev
+ * (caller buffers as any pbccs_zmw_output; add_read_results and zscores sized by the ZMW's n_reads) then hold what
+ * pbccs_polish_batch_ex2 returns for a ZMW of the same draft and SNR with only the strand-0 / strand-1 reads, in
+ * their original order and windows, both in the draft's orientation; per-read entries are indexed like the joint
+ * record's, -1 / NaN for the other strand's reads.  Not split: fwd and rev are left untouched. */
+typedef struct {
+    int n_sites;
+    int cap;
+    int* position;
+    int* type;
+    char* base;
+    double* sum_fwd;
+    double* sum_rev;
+    int split;
+    pbccs_zmw_output fwd, rev;
+} pbccs_strand_result;
+
+/* pbccs_polish_batch_ex2 with the strand screen: out is exactly pbccs_polish_batch_ex2's (the joint record is
+ * always produced), strand_out[i] the sites of ZMW i's final template (k_strand_sums and k_strand_sites beside the
+ * QV kernel, on the ConsensusQVs sweep's deltas) and, by strand->directional, its two per-strand records: the
+ * split ZMWs' single-strand inputs go through the same batch path and options (gates and repeats included; the
+ * rich QVs are the joint record's only) together.  strand NULL is the defaults.  pbccs_polish_extras keeps its
+ * layout: a caller built against the four-member struct stays valid, so the strand members travel beside it. */
+int pbccs_polish_batch_strand(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                              const pbccs_polish_extras* extras, const pbccs_strand_options* strand,
+                              pbccs_strand_result* strand_out, pbccs_zmw_output* out);
+
+/* pbccs_ccs_batch_ex4 (without windows: the windowed polish does not run the screen) with the strand screen, as
+ * pbccs_polish_batch_strand adds it to pbccs_polish_batch_ex2: the screen runs in each chunk's polish, the split
+ * ZMWs of all chunks are polished per strand together afterwards.  The per-read arrays of fwd / rev hold n_subreads
+ * entries indexed by the caller's subreads, like the joint record's. */
+int pbccs_ccs_batch_strand(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                           const pbccs_poa_options* poa, const pbccs_polish_options* opts,
+                           const pbccs_polish_extras* extras, const pbccs_strand_options* strand,
+                           pbccs_strand_result* strand_out, pbccs_ccs_output* out);
+
+/* The per-strand sums of n single-base mutations of the scorer's current template: one scoring round without a
+ * fast-score break, then k_strand_sums.  Bit-equal to summing pbccs_scorer_scores(m, 0) per strand in read order. */
+int pbccs_scorer_strand_scores(pbccs_scorer* s, const pbccs_mutation* m, int n, double* sum_fwd, double* sum_rev,
+                               int* n_fwd, int* n_rev);
+/* The discordant sites of the scorer's current template (the full unique-mutation sweep, as pbccs_consensus_qvs
+ * runs it).  *n = the sites; PBCCS_ERANGE when it exceeds cap (nothing is written).  opts NULL is the defaults;
+ * min_sites and directional are not used. */
+int pbccs_scorer_strand_sites(pbccs_scorer* s, const pbccs_strand_options* opts, int* position, int* type, char* base,
+                              double* sum_fwd, double* sum_rev, int cap, int* n);
+
+/* The screen's work since the last reset: ZMWs screened by the batch call, sites they reported, ZMWs split. */
+typedef struct {
+    long long strand_screened, strand_sites, strand_split;
+} pbccs_strand_stats;
+int pbccs_strand_stats_get(pbccs_engine* eng, pbccs_strand_stats* out, int reset);
+
 /* ---- consensus kinetics: per-strand mean IPD and pulse width -------------------------
  * An opt-in with no counterpart in the reference (2015 pbccs has no kinetics); csrc/kinetics_kernels.hpp states
  * the rules.  Frames are unsigned 16-bit counts.  A read placed on the consensus [tb, te) with its oriented

@@ -219,6 +219,22 @@ public:
     }
 };
 
+// The strand-discordance screen (no reference twin: the reference stops at the Directional TODO,
+// include/pacbio/ccs/Consensus.h:94-109).  StrandSums: the sums of Scores(m, 0) over the active forward / reverse reads
+// that score m, in AddRead order, and how many reads entered each.  StrandSite: a template position with a
+// single-base mutation one strand favours by more than minScore while the other opposes it by more than minScore.
+struct StrandSums {
+    double SumFwd, SumRev;
+    int NFwd, NRev;
+};
+struct StrandSite {
+    int Position;
+    MutationType Type;
+    char Base;   // '-' for a deletion
+    double SumFwd, SumRev;
+    Mutation ToMutation() const { return Mutation(Type, Position, Base); }
+};
+
 // DiploidSite / IsSiteHeterozygous (Arrow/Diploid.hpp:47-62, Diploid.cpp:94-241).  Position is this facade's
 // addition: the template position, set by the scorers' DiploidSites (-1 from IsSiteHeterozygous).
 struct DiploidSite {
@@ -395,6 +411,38 @@ public:
     {
         return diploid::DiploidSites(handle_, pbccs_scorer_diploid_sites, NumReads(), begin,
                                     end < 0 ? TemplateLength() : end, logPriorRatio, hostAll);
+    }
+    // Per-strand sums of single-base mutations (k_strand_sums): bit-equal to summing Scores(m, 0) per strand.
+    std::vector<StrandSums> StrandScores(const std::vector<Mutation>& muts)
+    {
+        const size_t n = muts.size();
+        std::vector<pbccs_mutation> c;
+        for (const Mutation& m : muts) c.push_back(m.ToC());
+        std::vector<double> sf(n), sr(n);
+        std::vector<int> nf(n), nr(n);
+        detail::Check(pbccs_scorer_strand_scores(handle_, c.data(), (int)n, sf.data(), sr.data(), nf.data(), nr.data()));
+        std::vector<StrandSums> out(n);
+        for (size_t i = 0; i < n; ++i) out[i] = StrandSums{sf[i], sr[i], nf[i], nr[i]};
+        return out;
+    }
+    // The strand-discordant sites of the current template, by ascending Position (the ConsensusQVs sweep, then
+    // k_strand_sums and k_strand_sites).
+    std::vector<StrandSite> StrandSites(double minScore = 12.5, int minReads = 2)
+    {
+        pbccs_strand_options o;
+        pbccs_strand_options_default(&o);
+        o.min_score = minScore;
+        o.min_reads = minReads;
+        const int cap = TemplateLength() > 0 ? TemplateLength() : 1;
+        std::vector<int> pos(cap), type(cap);
+        std::vector<char> base(cap);
+        std::vector<double> sf(cap), sr(cap);
+        int n = 0;
+        detail::Check(pbccs_scorer_strand_sites(handle_, &o, pos.data(), type.data(), base.data(), sf.data(), sr.data(),
+                                                cap, &n));
+        std::vector<StrandSite> out;
+        for (int k = 0; k < n; ++k) out.push_back(StrandSite{pos[k], (MutationType)type[k], base[k], sf[k], sr[k]});
+        return out;
     }
     pbccs_scorer* Handle() { return handle_; }
 

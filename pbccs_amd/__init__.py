@@ -285,6 +285,18 @@ class ArrowMultiReadMutationScorer:
         _lib_mod.check(load().pbccs_scorer_num_flipflops(self._h, out))
         return list(out[: self.NumReads()])
 
+    def StrandScores(self, muts):
+        """Per-strand sums of single-base mutations: StrandSums(sum_fwd, sum_rev, n_fwd, n_rev) per mutation, the
+        sums of Scores(m, 0) per strand in read order, bit for bit (k_strand_sums)."""
+        from . import strand
+        return strand.scorer_strand_scores(self, muts)
+
+    def StrandSites(self, min_score=12.5, min_reads=2):
+        """The strand-discordant sites of the current template: StrandSite(pos, type, base, sum_fwd, sum_rev) in
+        template order (the ConsensusQVs sweep, then k_strand_sums and k_strand_sites)."""
+        from . import strand
+        return strand.scorer_strand_sites(self, min_score, min_reads)
+
     def SiteScores(self, begin=0, end=None):
         """The site tensor of template positions [begin, end): float32 ndarray (sites, reads, 9), see diploid.py."""
         from . import diploid
@@ -369,6 +381,7 @@ from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac,
                     TargetToQueryPositions, UnsupportedFeatureError, align_band_stats, align_batch, align_stats)
 from .mapping import map_batch, map_stats, map_to_draft  # noqa: E402,F401
 from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa: E402,F401
+from .strand import StrandSite, StrandSums, strand_stats  # noqa: E402,F401
 from .kinetics import (codec_v1_decode, codec_v1_encode, kinetics_batch, kinetics_pileup,  # noqa: E402,F401
                        kinetics_stats)
 

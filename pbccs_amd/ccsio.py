@@ -139,7 +139,16 @@ def _f32(x):
                                                                ("inf" if x > 0 else "-inf"))
 
 
-def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False):
+def _ccs_name(movie, hole, strand):
+    """`movie/hole/ccs`, or `movie/hole/ccs/fwd` | `.../ccs/rev` for a per-strand record."""
+    if strand is None:
+        return f"{movie}/{hole}/ccs"
+    if strand not in ("fwd", "rev"):
+        raise ValueError('strand: None, "fwd" or "rev"')
+    return f"{movie}/{hole}/ccs/{strand}"
+
+
+def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=None):
     """The CCS record of src/main/ccs.cpp:105-172 as a SAM text line (unmapped, flag 4; MAPQ 255).
 
     result: one pbccs_amd polish result (status Success).  Tags in the reference's order: RG zm np rq sn pq
@@ -151,8 +160,10 @@ def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False):
     kinetics=True (a result made with kinetics=True): the consensus kinetics follow, after the rich tags when both
     are asked for, as fi fp (forward mean IPD / pulse width, B:C CodecV1 codes), fn (forward passes), ri rp (the
     same for the reverse strand, in the reverse strand's direction) and rn.
+    strand="fwd" | "rev" (result: the "fwd" / "rev" sub-record of a directional polish): the record
+    is named movie/hole/ccs/fwd or .../ccs/rev.
     """
-    name = f"{movie}/{hole}/ccs"
+    name = _ccs_name(movie, hole, strand)
     qual = QVsToASCII(result["qvs"])
     # zs: ZScores().second -- one entry per read the scorer took (inactive ones NaN), in AddRead order
     # (MultiReadMutationScorer.hpp:208-260).  ccs_batch results index their per-read arrays by subread and carry
@@ -188,9 +199,10 @@ def sam_header(movies, program="ccs", version="pbccs_amd"):
     return "\n".join(lines) + "\n"
 
 
-def ccs_fastq_record(movie, hole, result):
-    """`@movie/hole/ccs`, sequence, `+`, QVsToASCII(qvs)."""
-    return f"@{movie}/{hole}/ccs\n{result['consensus']}\n+\n{QVsToASCII(result['qvs'])}\n"
+def ccs_fastq_record(movie, hole, result, strand=None):
+    """`@movie/hole/ccs`, sequence, `+`, QVsToASCII(qvs); strand="fwd" | "rev" names a per-strand record
+    `@movie/hole/ccs/fwd` or `.../ccs/rev`."""
+    return f"@{_ccs_name(movie, hole, strand)}\n{result['consensus']}\n+\n{QVsToASCII(result['qvs'])}\n"
 
 
 def count_results(results, pre=None):

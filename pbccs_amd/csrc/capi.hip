@@ -58,6 +58,7 @@ struct pbccs_engine {
     long long oomRetries = 0;   // device batches rerun after PBCCS_EOOM
     long long repeatSkippedCkpt = 0;   // pbccs_polish_batch_ex: ZMWs whose repeat round a checkpointed read skipped
     DiploidStats diploid;       // the diploid screen's work (pbccs_diploid_stats_get)
+    long long strandScreened = 0, strandSites = 0, strandSplit = 0;   // pbccs_strand_stats_get
     long long createHostNs = 0, createUploadNs = 0;   // pbccs_batch_create: host setup / reservations + upload
     std::vector<std::unique_ptr<Workspace>> slots;
     // the POA draft step's device state (made on first use): kPoaSlices runners, one per concurrent slice
@@ -697,8 +698,15 @@ void pbccs_batch_destroy(pbccs_batch* b) { delete b; }
 
 // repTested / repApplied (b->n entries each, may be NULL): RefineRepeats' counts of a batch made with repeats
 // rich (b->n entries, may be NULL): the rich QVs of each ZMW beside its qvs (k_qv_rich instead of k_qv)
+// The strand screen of a span: its thresholds and, per ZMW, where its sites go.
+struct StrandScreen {
+    StrandOptions opt;
+    std::vector<StrandSiteH>* const* sites = nullptr;   // one vector per ZMW of the span (left empty without QVs)
+};
+
 static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTested = nullptr,
-                      long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
+                      long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr,
+                      const StrandScreen* strand = nullptr)
 {
     if (!b || (b->n > 0 && !out)) return fail(PBCCS_EINVAL, "bad argument");
     if (b->polished) return fail(PBCCS_ESTATE, "a batch polishes once");
@@ -784,7 +792,11 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
         // ConsensusQVs (Consensus.h:496-512) run inside the refine loop, in the round each ZMW converges
         std::vector<std::vector<int>> qvAll;
         std::vector<RichQVs> richAll, richQ;
-        B.Refine(refineZ, ro, &conv, &nt, &na, false, reclaim ? &qvAll : nullptr, reclaim && rich ? &richAll : nullptr);
+        std::vector<std::vector<StrandSiteH>> strandAll, strandQ;
+        B.Refine(refineZ, ro, &conv, &nt, &na, false, reclaim ? &qvAll : nullptr, reclaim && rich ? &richAll : nullptr,
+                 strand ? &strand->opt : nullptr, reclaim && strand ? &strandAll : nullptr);
+        if (strand)
+            for (int i = 0; i < n; ++i) strand->sites[i]->clear();
         std::vector<int> qvZ, qvIdx;
         std::vector<std::vector<int>> qvs;
         if (rich)
@@ -798,6 +810,7 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
                 qvIdx.push_back(refineIdx[k]);
                 if (reclaim) qvs.push_back(std::move(qvAll[k]));
                 if (reclaim && rich) richQ.push_back(std::move(richAll[k]));
+                if (reclaim && strand) strandQ.push_back(std::move(strandAll[k]));
             } else q.status = conv[k] < 0 ? PBCCS_ZMW_OTHER : PBCCS_ZMW_NON_CONVERGENT;
         }
         for (int i = 0; i < n; ++i) {
@@ -816,6 +829,7 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
             std::vector<int> rst;
             B.RefineRepeats(qvZ, b->repeats.repeat_length, b->repeats.min_repeat_elements, rr, &rt, &ra, &rconv, &rst);
             std::vector<int> keepZ, keepIdx;
+            std::vector<std::vector<StrandSiteH>> keepStrand;
             long long skipped = 0;
             for (size_t k = 0; k < qvZ.size(); ++k) {
                 if (repTested) repTested[qvIdx[k]] = rt[k];
@@ -827,15 +841,17 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
                 }
                 keepZ.push_back(qvZ[k]);
                 keepIdx.push_back(qvIdx[k]);
+                if (reclaim && strand) keepStrand.push_back(std::move(strandQ[k]));
             }
             qvZ.swap(keepZ);
             qvIdx.swap(keepIdx);
+            if (reclaim && strand) strandQ.swap(keepStrand);
             if (skipped) {
                 std::lock_guard<std::mutex> lk(b->eng->statsMu);
                 b->eng->repeatSkippedCkpt += skipped;
             }
         }
-        if (!reclaim) B.QVs(qvZ, &qvs, rich ? &richQ : nullptr);
+        if (!reclaim) B.QVs(qvZ, &qvs, rich ? &richQ : nullptr, strand ? &strand->opt : nullptr, strand ? &strandQ : nullptr);
         for (size_t k = 0; k < qvZ.size(); ++k) {
             pbccs_zmw_output& q = out[qvIdx[k]];
             const std::string& t = B.Template(qvZ[k]);
@@ -856,6 +872,7 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
             }
             if (q.qvs) std::copy(qvs[k].begin(), qvs[k].end(), q.qvs);
             q.status = (acc < o.min_predicted_accuracy) ? PBCCS_ZMW_POOR_QUALITY : PBCCS_ZMW_SUCCESS;
+            if (strand) *strand->sites[qvIdx[k]] = std::move(strandQ[k]);
         }
         return PBCCS_OK;
     });
@@ -864,11 +881,12 @@ static int polish_one(pbccs_batch* b, pbccs_zmw_output* out, long long* repTeste
 // Create, polish, account and destroy one device batch of m ZMWs on `slot`.
 static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int m, const pbccs_polish_options* o,
                        pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
-                       long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
+                       long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr,
+                       const StrandScreen* strand = nullptr)
 {
     pbccs_batch* h = nullptr;
     int r = create_batch(eng, in, m, o, slot, &h, repeats);
-    if (r == PBCCS_OK) r = polish_one(h, out, repTested, repApplied, rich);
+    if (r == PBCCS_OK) r = polish_one(h, out, repTested, repApplied, rich, strand);
     if (h) {
         if (h->B) merge_engine_stats(eng, *h->B);
         pbccs_batch_destroy(h);
@@ -882,7 +900,8 @@ static int polish_span(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, i
 // the retry changes the schedule and nothing else.  Outputs land in out[0..n) in input order.
 static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, int n, const pbccs_polish_options* o,
                         pbccs_zmw_output* out, const pbccs_repeat_options* repeats = nullptr,
-                        long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr)
+                        long long* repTested = nullptr, long long* repApplied = nullptr, pbccs_rich_qvs* rich = nullptr,
+                        const StrandScreen* strand = nullptr)
 {
     std::vector<std::pair<int, int>> todo{{0, n}};
     // the slot's outgrown buffers go back to the device before the rerun (nothing of the slot is queued: its batches
@@ -895,10 +914,15 @@ static int polish_retry(pbccs_engine* eng, int slot, const pbccs_zmw_input* in, 
             std::lock_guard<std::mutex> lk(eng->statsMu);
             eng->oomRetries += 1;
         }
+        StrandScreen sub;
+        if (strand) {
+            sub.opt = strand->opt;
+            sub.sites = strand->sites + span.first;
+        }
         const int r = polish_span(eng, slot, in + span.first, span.second - span.first, o, out + span.first, repeats,
                                   repTested ? repTested + span.first : nullptr,
                                   repApplied ? repApplied + span.first : nullptr,
-                                  rich ? rich + span.first : nullptr);
+                                  rich ? rich + span.first : nullptr, strand ? &sub : nullptr);
         if (r == PBCCS_OK) continue;
         if (r != PBCCS_EOOM || span.second - span.first < 2) return r;
         eng->Slot(slot)->val.unmap_all();
@@ -1106,10 +1130,14 @@ int pbccs_plan_batches(const pbccs_zmw_input* in, int n, double budget_bytes, in
 // pbccs_polish_batch (repeats == NULL) and pbccs_polish_batch_ex: the ZMW work queue
 static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
                              const pbccs_repeat_options* repeats, long long* repTested, long long* repApplied,
-                             pbccs_zmw_output* out, pbccs_rich_qvs* rich = nullptr)
+                             pbccs_zmw_output* out, pbccs_rich_qvs* rich = nullptr,
+                             const StrandOptions* strandOpt = nullptr,
+                             std::vector<std::vector<StrandSiteH>>* strandSites = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
     if (n == 0) return PBCCS_OK;
+    if (!(strandOpt && strandSites)) strandOpt = nullptr;
+    if (strandOpt) strandSites->assign(n, {});
     pbccs_polish_options o;
     pbccs_polish_options_default(&o);
     if (opts) o = *opts;
@@ -1167,6 +1195,13 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
         br->resize(rich ? e - b : 0);
         for (int k = 0; rich && k < e - b; ++k) (*br)[k] = rich[order[b + k]];
     };
+    // the strand screen of a span: the sites land in the caller's per-ZMW vectors directly
+    auto gather_strand = [&](int b, int e, std::vector<std::vector<StrandSiteH>*>* bs, StrandScreen* sc) {
+        bs->resize(strandOpt ? e - b : 0);
+        for (int k = 0; strandOpt && k < e - b; ++k) (*bs)[k] = &(*strandSites)[order[b + k]];
+        if (strandOpt) sc->opt = *strandOpt;
+        sc->sites = bs->data();
+    };
     auto scatter_rich = [&](int b, int e, const std::vector<pbccs_rich_qvs>& br) {
         for (int k = 0; rich && k < e - b; ++k) rich[order[b + k]] = br[k];
     };
@@ -1186,6 +1221,8 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
         std::vector<pbccs_zmw_output> bout;
         std::vector<long long> brt, bra;
         std::vector<pbccs_rich_qvs> brich;
+        std::vector<std::vector<StrandSiteH>*> bstrand;
+        StrandScreen screen;
         for (;;) {
             const int b = next.fetch_add(1);
             if (b >= nb || stop.load()) return;
@@ -1193,6 +1230,7 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
             try {
                 gather(start[b], start[b + 1], &bin, &bout);
                 gather_rich(start[b], start[b + 1], &brich);
+                gather_strand(start[b], start[b + 1], &bstrand, &screen);
                 if (repeats) {
                     brt.assign(start[b + 1] - start[b], 0);
                     bra.assign(start[b + 1] - start[b], 0);
@@ -1203,7 +1241,7 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
             if (r == PBCCS_OK)
                 r = polish_span(eng, slot, bin.data(), start[b + 1] - start[b], &o, bout.data(), repeats,
                                 repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr,
-                                rich ? brich.data() : nullptr);
+                                rich ? brich.data() : nullptr, strandOpt ? &screen : nullptr);
             if (r == PBCCS_OK) {
                 scatter(start[b], start[b + 1], bout);
                 scatter_rich(start[b], start[b + 1], brich);
@@ -1237,13 +1275,16 @@ static int polish_batch_impl(pbccs_engine* eng, const pbccs_zmw_input* in, int n
             std::vector<pbccs_zmw_input> bin;
             std::vector<pbccs_zmw_output> bout;
             std::vector<pbccs_rich_qvs> brich;
+            std::vector<std::vector<StrandSiteH>*> bstrand;
+            StrandScreen screen;
             for (const std::pair<int, int>& span : deferred) {
                 gather(span.first, span.second, &bin, &bout);
                 gather_rich(span.first, span.second, &brich);
+                gather_strand(span.first, span.second, &bstrand, &screen);
                 std::vector<long long> brt(span.second - span.first, 0), bra(span.second - span.first, 0);
                 const int r = polish_retry(eng, 0, bin.data(), span.second - span.first, &o, bout.data(), repeats,
                                            repeats ? brt.data() : nullptr, repeats ? bra.data() : nullptr,
-                                           rich ? brich.data() : nullptr);
+                                           rich ? brich.data() : nullptr, strandOpt ? &screen : nullptr);
                 if (r != PBCCS_OK) return r;
                 scatter(span.first, span.second, bout);
                 scatter_rich(span.first, span.second, brich);
@@ -1280,6 +1321,233 @@ int pbccs_polish_batch_ex2(pbccs_engine* eng, const pbccs_zmw_input* in, int n, 
         return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
     return polish_batch_impl(eng, in, n, opts, x.repeats, x.repeats ? x.repeat_tested : nullptr,
                              x.repeats ? x.repeat_applied : nullptr, out, x.rich);
+}
+
+// ---- directional consensus ----------------------------------------------------------------
+void pbccs_strand_options_default(pbccs_strand_options* o)
+{
+    if (!o) return;
+    o->min_score = 12.5;
+    o->min_reads = 2;
+    o->min_sites = 1;
+    o->directional = 0;
+}
+
+static bool strand_options_ok(const pbccs_strand_options& o)
+{
+    return o.min_score >= 0.0 && o.min_reads >= 0 && o.min_sites >= 0 && o.directional >= 0 && o.directional <= 2;
+}
+
+static StrandOptions strand_engine_options(const pbccs_strand_options& o)
+{
+    StrandOptions e;
+    e.minScore = o.min_score;
+    e.minReads = o.min_reads;
+    return e;
+}
+
+// After a joint polish that ran the screen (sites[i]: ZMW i's sites): the sites into sres[i]'s buffers, the split
+// decision, and the split ZMWs' single-strand inputs, forward then reverse per ZMW, through the same batch path
+// together.  sres[i].fwd / rev take per-read entries by position in in[i]'s reads.  PBCCS_ERANGE (after every output
+// is written) when a ZMW's site buffers are too small.
+static int strand_finish(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                         const pbccs_repeat_options* repeats, const pbccs_strand_options& so,
+                         const std::vector<std::vector<StrandSiteH>>& sites, const pbccs_zmw_output* out,
+                         pbccs_strand_result* sres)
+{
+    return guarded([&] {
+        bool range = false;
+        long long screened = 0, nSites = 0;
+        std::vector<int> split;
+        for (int i = 0; i < n; ++i) {
+            pbccs_strand_result& r = sres[i];
+            const bool hasQvs = out[i].status == PBCCS_ZMW_SUCCESS || out[i].status == PBCCS_ZMW_POOR_QUALITY;
+            if (!hasQvs) continue;
+            ++screened;
+            const std::vector<StrandSiteH>& v = sites[i];
+            const int m = (int)v.size();
+            nSites += m;
+            if (m > r.cap || (m > 0 && (!r.position || !r.type || !r.base || !r.sum_fwd || !r.sum_rev))) {
+                r.n_sites = -m;
+                range = true;
+            } else {
+                for (int k = 0; k < m; ++k) {
+                    r.position[k] = v[k].pos;
+                    r.type[k] = v[k].type;
+                    r.base[k] = v[k].base;
+                    r.sum_fwd[k] = v[k].sumF;
+                    r.sum_rev[k] = v[k].sumR;
+                }
+                r.n_sites = m;
+            }
+            if (so.directional == 2 || (so.directional == 1 && m >= so.min_sites)) split.push_back(i);
+        }
+        const int ns = (int)split.size();
+        struct Sub {
+            std::vector<const char*> seqs;
+            std::vector<int> lens, strands, ts, te, idx, arr;
+            std::vector<unsigned char> fp;
+            std::vector<double> zs;
+        };
+        std::vector<Sub> subs(2 * ns);
+        std::vector<pbccs_zmw_input> sin(2 * ns);
+        std::vector<pbccs_zmw_output> sout(2 * ns);
+        for (int q = 0; q < 2 * ns; ++q) {
+            const int i = split[q / 2], want = q & 1;
+            const pbccs_zmw_input& z = in[i];
+            Sub& u = subs[q];
+            for (int k = 0; k < z.n_reads; ++k) {
+                if ((z.strands[k] ? 1 : 0) != want) continue;
+                u.seqs.push_back(z.seqs[k]);
+                u.lens.push_back(z.lens[k]);
+                u.strands.push_back(z.strands[k]);
+                u.ts.push_back(z.tstarts[k]);
+                u.te.push_back(z.tends[k]);
+                u.fp.push_back(z.full_pass ? z.full_pass[k] : 1);
+                u.idx.push_back(k);
+            }
+            u.arr.assign(u.idx.size() + 1, -1);
+            u.zs.assign(u.idx.size() + 1, std::numeric_limits<double>::quiet_NaN());
+            pbccs_zmw_input& s = sin[q];
+            s = z;
+            s.n_reads = (int)u.idx.size();
+            s.seqs = u.seqs.data();
+            s.lens = u.lens.data();
+            s.strands = u.strands.data();
+            s.tstarts = u.ts.data();
+            s.tends = u.te.data();
+            s.full_pass = u.fp.data();
+            pbccs_zmw_output& o = sout[q];
+            o = want ? sres[i].rev : sres[i].fwd;
+            o.add_read_results = u.arr.data();
+            o.zscores = u.zs.data();
+        }
+        if (ns > 0) {
+            std::vector<long long> rt(2 * ns, 0), ra(2 * ns, 0);
+            const int r2 = polish_batch_impl(eng, sin.data(), 2 * ns, opts, repeats, repeats ? rt.data() : nullptr,
+                                             repeats ? ra.data() : nullptr, sout.data());
+            if (r2 != PBCCS_OK) return r2;
+        }
+        for (int q = 0; q < 2 * ns; ++q) {
+            const int i = split[q / 2];
+            pbccs_zmw_output& dst = (q & 1) ? sres[i].rev : sres[i].fwd;
+            int* const arr = dst.add_read_results;
+            double* const zs = dst.zscores;
+            dst = sout[q];
+            dst.add_read_results = arr;
+            dst.zscores = zs;
+            // per-read entries indexed like the joint record's: -1 / NaN for the other strand's reads
+            for (int k = 0; k < in[i].n_reads; ++k) {
+                if (arr) arr[k] = -1;
+                if (zs) zs[k] = std::numeric_limits<double>::quiet_NaN();
+            }
+            const Sub& u = subs[q];
+            for (size_t j = 0; j < u.idx.size(); ++j) {
+                if (arr) arr[u.idx[j]] = u.arr[j];
+                if (zs) zs[u.idx[j]] = u.zs[j];
+            }
+            sres[i].split = 1;
+        }
+        {
+            std::lock_guard<std::mutex> lk(eng->statsMu);
+            eng->strandScreened += screened;
+            eng->strandSites += nSites;
+            eng->strandSplit += ns;
+        }
+        return range ? fail(PBCCS_ERANGE, "strand site buffers too small") : PBCCS_OK;
+    });
+}
+
+int pbccs_polish_batch_strand(pbccs_engine* eng, const pbccs_zmw_input* in, int n, const pbccs_polish_options* opts,
+                              const pbccs_polish_extras* extras, const pbccs_strand_options* strand,
+                              pbccs_strand_result* strand_out, pbccs_zmw_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out || !strand_out))) return fail(PBCCS_EINVAL, "bad argument");
+    const pbccs_polish_extras none{};
+    const pbccs_polish_extras& x = extras ? *extras : none;
+    if (x.repeats && (x.repeats->repeat_length < 1 || x.repeats->repeat_length > PBCCS_MAX_MUTATION_BASES))
+        return fail(PBCCS_EINVAL, "repeat_length must be 1..7");
+    pbccs_strand_options so;
+    pbccs_strand_options_default(&so);
+    if (strand) so = *strand;
+    if (!strand_options_ok(so))
+        return fail(PBCCS_EINVAL, "strand options: min_score, min_reads, min_sites >= 0, directional 0..2");
+    for (int i = 0; i < n; ++i) {
+        if (in[i].n_reads > 0 && !in[i].strands) return fail(PBCCS_EINVAL, "bad pbccs_zmw_input");
+        strand_out[i].n_sites = 0;
+        strand_out[i].split = 0;
+    }
+    const StrandOptions eo = strand_engine_options(so);
+    std::vector<std::vector<StrandSiteH>> sites;
+    const int rc = polish_batch_impl(eng, in, n, opts, x.repeats, x.repeats ? x.repeat_tested : nullptr,
+                                     x.repeats ? x.repeat_applied : nullptr, out, x.rich, &eo, &sites);
+    if (rc != PBCCS_OK) return rc;
+    return strand_finish(eng, in, n, opts, x.repeats, so, sites, out, strand_out);
+}
+
+int pbccs_scorer_strand_scores(pbccs_scorer* s, const pbccs_mutation* m, int n, double* sum_fwd, double* sum_rev,
+                               int* n_fwd, int* n_rev)
+{
+    if (!s || n < 0 || (n > 0 && (!m || !sum_fwd || !sum_rev || !n_fwd || !n_rev))) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        ArrowBatch& B = *s->batch;
+        const int L = (int)B.Template(s->z).size();
+        std::vector<int> codes;
+        for (int i = 0; i < n; ++i) {
+            Mutation mu;
+            if (!to_mutation(m[i], L, &mu)) return fail(PBCCS_EINVAL, "invalid single-base mutation");
+            codes.push_back(mutation_code(mu));
+        }
+        StrandSumsH h;
+        B.StrandScores(s->z, codes, &h);
+        for (int i = 0; i < n; ++i) {
+            sum_fwd[i] = h.sumF[i];
+            sum_rev[i] = h.sumR[i];
+            n_fwd[i] = h.nF[i];
+            n_rev[i] = h.nR[i];
+        }
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_scorer_strand_sites(pbccs_scorer* s, const pbccs_strand_options* opts, int* position, int* type, char* base,
+                              double* sum_fwd, double* sum_rev, int cap, int* n)
+{
+    if (!s || !n || cap < 0) return fail(PBCCS_EINVAL, "bad argument");
+    pbccs_strand_options so;
+    pbccs_strand_options_default(&so);
+    if (opts) so = *opts;
+    if (!strand_options_ok(so)) return fail(PBCCS_EINVAL, "strand options: min_score, min_reads >= 0");
+    return guarded([&] {
+        StrandOptions eo;
+        eo.minScore = so.min_score;
+        eo.minReads = so.min_reads;
+        std::vector<std::vector<int>> q;
+        std::vector<std::vector<StrandSiteH>> v;
+        s->batch->QVs({s->z}, &q, nullptr, &eo, &v);
+        *n = (int)v[0].size();
+        if (*n > cap || (*n > 0 && (!position || !type || !base || !sum_fwd || !sum_rev)))
+            return fail(PBCCS_ERANGE, "buffer too small");
+        for (int k = 0; k < *n; ++k) {
+            position[k] = v[0][k].pos;
+            type[k] = v[0][k].type;
+            base[k] = v[0][k].base;
+            sum_fwd[k] = v[0][k].sumF;
+            sum_rev[k] = v[0][k].sumR;
+        }
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_strand_stats_get(pbccs_engine* eng, pbccs_strand_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lock(eng->statsMu);
+    out->strand_screened = eng->strandScreened;
+    out->strand_sites = eng->strandSites;
+    out->strand_split = eng->strandSplit;
+    if (reset) eng->strandScreened = eng->strandSites = eng->strandSplit = 0;
+    return PBCCS_OK;
 }
 
 int pbccs_engine_set_profiling(pbccs_engine* eng, int on)
@@ -3672,6 +3940,9 @@ struct CcsChunk {
     std::vector<int> pinZ;
     std::vector<pbccs_zmw_output> pout;
     std::vector<pbccs_rich_qvs> prich;   // a rich call: the caller's rich-QV structs of the ZMWs in pin
+    // a strand call: the screen's sites of the ZMWs in pin, and the pointers polish_span takes
+    std::vector<std::vector<StrandSiteH>> psites;
+    std::vector<std::vector<StrandSiteH>*> psitePtr;
     // per-read polish outputs by position in the polish input (FilterReads order up to the maxPoaCov stop);
     // scattered back to the caller's subread order once the chunk's polish is final
     std::vector<std::vector<int>> arr;
@@ -3814,10 +4085,23 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
 static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
                           bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out,
                           const pbccs_window_options* win = nullptr, pbccs_window_info* info = nullptr,
-                          pbccs_rich_qvs* rich = nullptr)
+                          pbccs_rich_qvs* rich = nullptr, const pbccs_strand_options* strand = nullptr,
+                          pbccs_strand_result* sres = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
+    if (strand && (win || !sres || !strand_options_ok(*strand)))
+        return fail(PBCCS_EINVAL, "the strand screen takes no windows, needs its outputs and valid options");
     for (int z = 0; rich && z < n; ++z) rich[z].len = 0;   // ZMWs that never reach the polish
+    for (int z = 0; strand && z < n; ++z) sres[z].n_sites = sres[z].split = 0;
+    StrandOptions strandEng;
+    if (strand) strandEng = strand_engine_options(*strand);
+    // the screen of the chunk's polish inputs [lo, lo + ...)
+    auto chunk_screen = [&](CcsChunk& C, int lo) {
+        StrandScreen sc;
+        sc.opt = strandEng;
+        sc.sites = strand ? C.psitePtr.data() + lo : nullptr;
+        return sc;
+    };
     if (win && !window_options_ok(win))
         return fail(PBCCS_EINVAL, "window options: need window > overlap >= 2 guard, guard >= 1, 4 <= k <= 8");
     if (win && info)
@@ -3949,8 +4233,9 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 CcsChunk& C = chunks[c];
                 if (hi <= lo) continue;
                 const double p0 = since();
+                const StrandScreen sc = chunk_screen(C, lo);
                 const int rc = polish_span(eng, slot, C.pin.data() + lo, hi - lo, &o, C.pout.data() + lo, nullptr, nullptr,
-                                           nullptr, rich ? C.prich.data() + lo : nullptr);
+                                           nullptr, rich ? C.prich.data() + lo : nullptr, strand ? &sc : nullptr);
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d polish slot %d zmws %d %.1f-%.1f ms\n", c, slot, hi - lo, p0,
                                  since());
@@ -3986,6 +4271,10 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, bandedPoa, sub, order, out, &chunks[c]);
                 if (rich)
                     for (int z : chunks[c].pinZ) chunks[c].prich.push_back(rich[z]);
+                if (strand) {
+                    chunks[c].psites.assign(chunks[c].pinZ.size(), {});
+                    for (std::vector<StrandSiteH>& v : chunks[c].psites) chunks[c].psitePtr.push_back(&v);
+                }
                 if (trace)
                     std::fprintf(stderr, "[ccs] chunk %d draft zmws %zu %.1f-%.1f ms\n", c, chunks[c].zs.size(), d0,
                                  since());
@@ -4055,8 +4344,9 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             }
             CcsChunk& C = chunks[c];
             bind_polish_outputs(&C, out);
+            const StrandScreen sc = chunk_screen(C, 0);
             const int r = polish_retry(eng, 0, C.pin.data(), (int)C.pin.size(), &o, C.pout.data(), nullptr, nullptr,
-                                       nullptr, rich ? C.prich.data() : nullptr);
+                                       nullptr, rich ? C.prich.data() : nullptr, strand ? &sc : nullptr);
             if (r != PBCCS_OK) return r;
         }
         bool draftRange = false;
@@ -4083,7 +4373,69 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 }
             }
         }
-        return draftRange ? fail(PBCCS_ERANGE, "draft buffer too small") : PBCCS_OK;
+        // the strand screen's second half over the polish inputs of every chunk: sites, split
+        // decision, the per-strand polish; per-read entries go from polish positions back to the caller's subreads
+        int strandRc = PBCCS_OK;
+        if (strand) {
+            std::vector<pbccs_zmw_input> pin;
+            std::vector<pbccs_zmw_output> pout;
+            std::vector<std::vector<StrandSiteH>> sites;
+            std::vector<pbccs_strand_result> pres;
+            std::vector<int> pz;
+            for (CcsChunk& C : chunks)
+                for (size_t q = 0; q < C.pinZ.size(); ++q) {
+                    pin.push_back(C.pin[q]);
+                    pout.push_back(out[C.pinZ[q]].polish);
+                    sites.push_back(std::move(C.psites[q]));
+                    pres.push_back(sres[C.pinZ[q]]);
+                    pz.push_back(C.pinZ[q]);
+                }
+            const size_t np = pin.size();
+            std::vector<std::vector<int>> arrF(np), arrR(np);
+            std::vector<std::vector<double>> zsF(np), zsR(np);
+            for (size_t q = 0; q < np; ++q) {
+                const size_t m = (size_t)std::max(1, pin[q].n_reads);
+                arrF[q].assign(m, -1);
+                arrR[q].assign(m, -1);
+                zsF[q].assign(m, std::numeric_limits<double>::quiet_NaN());
+                zsR[q].assign(m, std::numeric_limits<double>::quiet_NaN());
+                pres[q].fwd.add_read_results = arrF[q].data();
+                pres[q].rev.add_read_results = arrR[q].data();
+                pres[q].fwd.zscores = zsF[q].data();
+                pres[q].rev.zscores = zsR[q].data();
+            }
+            strandRc = strand_finish(eng, pin.data(), (int)np, &o, nullptr, *strand, sites, pout.data(), pres.data());
+            if (strandRc != PBCCS_OK && strandRc != PBCCS_ERANGE) return strandRc;
+            for (size_t q = 0; q < np; ++q) {
+                const int z = pz[q];
+                pbccs_strand_result& dst = sres[z];
+                dst.n_sites = pres[q].n_sites;
+                dst.split = pres[q].split;
+                if (!dst.split) continue;
+                for (int side = 0; side < 2; ++side) {
+                    pbccs_zmw_output& d = side ? dst.rev : dst.fwd;
+                    int* const arr = d.add_read_results;
+                    double* const zs = d.zscores;
+                    d = side ? pres[q].rev : pres[q].fwd;
+                    d.add_read_results = arr;
+                    d.zscores = zs;
+                    for (int r = 0; r < in[z].n_subreads; ++r) {
+                        if (arr) arr[r] = -1;
+                        if (zs) zs[r] = std::numeric_limits<double>::quiet_NaN();
+                    }
+                    const std::vector<int>& a = side ? arrR[q] : arrF[q];
+                    const std::vector<double>& v = side ? zsR[q] : zsF[q];
+                    for (int i = 0; i < pin[q].n_reads; ++i) {
+                        const int k = order[z][i];
+                        if (k < 0) continue;
+                        if (arr) arr[k] = a[i];
+                        if (zs) zs[k] = v[i];
+                    }
+                }
+            }
+        }
+        if (draftRange) return fail(PBCCS_ERANGE, "draft buffer too small");
+        return strandRc == PBCCS_ERANGE ? fail(PBCCS_ERANGE, "strand site buffers too small") : PBCCS_OK;
     });
 }
 
@@ -4139,6 +4491,23 @@ int pbccs_ccs_batch_ex4(pbccs_engine* eng, const pbccs_ccs_input* in, int n, con
     else pbccs_ccs_options_default(&c);
     return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out, win,
                           info, extras ? extras->rich : nullptr);
+}
+
+int pbccs_ccs_batch_strand(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                           const pbccs_poa_options* poa, const pbccs_polish_options* opts,
+                           const pbccs_polish_extras* extras, const pbccs_strand_options* strand,
+                           pbccs_strand_result* strand_out, pbccs_ccs_output* out)
+{
+    if (n > 0 && !strand_out) return fail(PBCCS_EINVAL, "bad argument");
+    if (extras && extras->repeats) return fail(PBCCS_EINVAL, "the ccs calls take no repeat options");
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    pbccs_strand_options so;
+    pbccs_strand_options_default(&so);
+    if (strand) so = *strand;
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out,
+                          nullptr, nullptr, extras ? extras->rich : nullptr, &so, strand_out);
 }
 
 }  // extern "C"

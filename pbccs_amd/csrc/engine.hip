@@ -2,6 +2,7 @@
 #include "engine.hpp"
 #include "diploid_kernels.hpp"
 #include "refine_repeats.hpp"
+#include "strand_kernels.hpp"
 
 #include <hipcub/hipcub.hpp>
 
@@ -29,7 +30,8 @@ namespace pbccs {
 const char* const kKernelNames[kKernelKinds] = {"k_fill",       "k_suffix",      "k_enumerate", "k_score",
                                                  "k_reduce",     "k_qv",          "k_best_subset", "k_compact",
                                                  "k_fill_tall",  "k_qfill_grp",   "k_qfill_coop", "k_qfill",
-                                                 "k_qscore_mid", "k_qscore_multi", "k_score_wide", "k_qv_rich"};
+                                                 "k_qscore_mid", "k_qscore_multi", "k_score_wide", "k_qv_rich",
+                                                 "k_strand_sums", "k_strand_sites"};
 
 namespace {
 
@@ -1926,6 +1928,47 @@ void ArrowBatch::ScoreLists(const std::vector<int>& zl, const std::vector<std::v
     }
 }
 
+void ArrowBatch::StrandScores(int zi, const std::vector<int>& codes, StrandSumsH* out)
+{
+    const StreamScope bound(stream_);
+    const size_t n = codes.size();
+    out->sumF.assign(n, 0.0);
+    out->sumR.assign(n, 0.0);
+    out->nF.assign(n, 0);
+    out->nR.assign(n, 0);
+    if (n == 0) return;
+    const std::vector<std::vector<int>> lists{codes};
+    RunRound({zi}, &lists, -std::numeric_limits<double>::max(), false);
+    ScoreWork W;
+    W.nWork = 1;
+    W.zmw = dWZmw_.ptr;
+    W.nMut = dWNMut_.ptr;
+    W.mutBase = dWMutBase_.ptr;
+    W.deltaBase = dWDeltaBase_.ptr;
+    W.mutStart = dWMutStart_.ptr;
+    W.codes = dCodes_.ptr;
+    W.delta = dDelta_.ptr;
+    dStrandD_.reserve(2 * n, false);
+    dStrandI_.reserve(2 * n, false);
+    StrandSums S;
+    S.sumF = dStrandD_.ptr;
+    S.sumR = dStrandD_.ptr + n;
+    S.nF = dStrandI_.ptr;
+    S.nR = dStrandI_.ptr + n;
+    const DevBatch B = View();
+    Timed(kKStrandSums, [&] { launch_strand_sums(B, W, (long long)n, S, stream_); });
+    PBCCS_HIP(hipGetLastError());
+    std::vector<double> d(2 * n);
+    std::vector<int> c(2 * n);
+    d2h(d.data(), dStrandD_.ptr, 2 * n * sizeof(double), stream_);
+    d2h(c.data(), dStrandI_.ptr, 2 * n * sizeof(int), stream_);
+    PBCCS_HIP(hipStreamSynchronize(stream_));
+    std::copy(d.begin(), d.begin() + n, out->sumF.begin());
+    std::copy(d.begin() + n, d.end(), out->sumR.begin());
+    std::copy(c.begin(), c.begin() + n, out->nF.begin());
+    std::copy(c.begin() + n, c.end(), out->nR.begin());
+}
+
 // ------------------------------------------------------------------------------------------------
 // Diploid site calling (Arrow/Diploid.cpp:94-241)
 // ------------------------------------------------------------------------------------------------
@@ -2300,13 +2343,16 @@ bool best_subset_certain(const std::vector<Scored>& in, const std::vector<double
 
 void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std::vector<int>* converged,
                         std::vector<long long>* nTested, std::vector<long long>* nApplied, bool needFinalState,
-                        std::vector<std::vector<int>>* qvsOnConverge, std::vector<RichQVs>* richOnConverge)
+                        std::vector<std::vector<int>>* qvsOnConverge, std::vector<RichQVs>* richOnConverge,
+                        const StrandOptions* strand, std::vector<std::vector<StrandSiteH>>* strandOnConverge)
 {
     const StreamScope bound(stream_);
     const int n = (int)zl.size();
     converged->assign(n, 0);
     if (qvsOnConverge) qvsOnConverge->assign(n, {});
     if (qvsOnConverge && richOnConverge) richOnConverge->assign(n, {});
+    if (!(qvsOnConverge && strand)) strandOnConverge = nullptr;
+    if (strandOnConverge) strandOnConverge->assign(n, {});
     // ZMWs whose bands nobody reads again once they are done (needFinalState = false: the batch polish reads
     // only converged ZMWs, through their QVs): retired so the reclaiming layout can drop them
     const bool retireDone = reclaim_ && !needFinalState;
@@ -2663,8 +2709,12 @@ void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std
         if (!qvNow.empty()) {
             std::vector<std::vector<int>> q;
             std::vector<RichQVs> rq;
-            QVs(qvNow, &q, richOnConverge ? &rq : nullptr);
+            std::vector<std::vector<StrandSiteH>> sq;
+            QVs(qvNow, &q, richOnConverge ? &rq : nullptr, strandOnConverge ? strand : nullptr,
+                strandOnConverge ? &sq : nullptr);
             for (size_t i = 0; i < qvNow.size(); ++i) (*qvsOnConverge)[qvIdx[i]] = std::move(q[i]);
+            if (strandOnConverge)
+                for (size_t i = 0; i < qvNow.size(); ++i) (*strandOnConverge)[qvIdx[i]] = std::move(sq[i]);
             if (richOnConverge)
                 for (size_t i = 0; i < qvNow.size(); ++i) (*richOnConverge)[qvIdx[i]] = std::move(rq[i]);
             if (reclaim_) Retire(qvNow);
@@ -2695,7 +2745,8 @@ void ArrowBatch::Refine(const std::vector<int>& zl, const RefineOptions& ro, std
 // ------------------------------------------------------------------------------------------------
 // ConsensusQVs
 // ------------------------------------------------------------------------------------------------
-void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich)
+void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich,
+                     const StrandOptions* strand, std::vector<std::vector<StrandSiteH>>* sites)
 {
     const StreamScope bound(stream_);
     RunRound(zl, nullptr, -std::numeric_limits<double>::max(), true);
@@ -2735,10 +2786,57 @@ void ArrowBatch::QVs(const std::vector<int>& zl, std::vector<std::vector<int>>* 
         });
     }
     PBCCS_HIP(hipGetLastError());
+    // the strand-discordance screen: the same round's deltas summed per strand, then one thread
+    // per position; [0, 2 nMut) of each array are k_strand_sums', the nPos-sized pairs behind them k_strand_sites'
+    const bool screen = strand && sites;
+    const size_t nMut = (size_t)rTotalMut_;
+    if (screen) {
+        dStrandD_.reserve(std::max<size_t>(2 * nMut + 2 * nPos, 1), false);
+        dStrandI_.reserve(std::max<size_t>(2 * nMut + 2 * nPos, 1), false);
+        StrandSums S;
+        S.sumF = dStrandD_.ptr;
+        S.sumR = dStrandD_.ptr + nMut;
+        S.nF = dStrandI_.ptr;
+        S.nR = dStrandI_.ptr + nMut;
+        StrandSiteOut O;
+        O.sumF = dStrandD_.ptr + 2 * nMut;
+        O.sumR = dStrandD_.ptr + 2 * nMut + nPos;
+        O.flag = dStrandI_.ptr + 2 * nMut;
+        O.code = dStrandI_.ptr + 2 * nMut + nPos;
+        Timed(kKStrandSums, [&] { launch_strand_sums(B, W, rTotalMut_, S, stream_); });
+        Timed(kKStrandSites, [&] {
+            launch_strand_sites(W, rTotalPos_, dWPosBase_.ptr, dPosOff_.ptr, S, dWQvBase_.ptr, strand->minScore,
+                                strand->minReads, O, stream_);
+        });
+        PBCCS_HIP(hipGetLastError());
+    }
     std::vector<int> q, rq;
     download(q, dQv_, rTotalPos_, stream_);
     if (rich) download(rq, dRich_, richInts, stream_);
+    std::vector<int> sFlag;      // flag then code, nPos each
+    std::vector<double> sSum;    // sumF then sumR, nPos each
+    if (screen && nPos > 0) {
+        sFlag.resize(2 * nPos);
+        sSum.resize(2 * nPos);
+        d2h(sFlag.data(), dStrandI_.ptr + 2 * nMut, 2 * nPos * sizeof(int), stream_);
+        d2h(sSum.data(), dStrandD_.ptr + 2 * nMut, 2 * nPos * sizeof(double), stream_);
+    }
     PBCCS_HIP(hipStreamSynchronize(stream_));
+    if (screen) {
+        sites->assign(zl.size(), {});
+        for (size_t k = 0; k < zl.size(); ++k)
+            for (long long p = rPosStart_[k]; p < rPosStart_[k + 1]; ++p) {
+                if (!sFlag[p]) continue;
+                const int code = sFlag[nPos + p];
+                StrandSiteH h;
+                h.pos = mut_pos(code);
+                h.type = mut_type(code);
+                h.base = h.type == kDel ? '-' : base_char(mut_base(code));
+                h.sumF = sSum[p];
+                h.sumR = sSum[nPos + p];
+                (*sites)[k].push_back(h);
+            }
+    }
     qvs->assign(zl.size(), {});
     for (size_t k = 0; k < zl.size(); ++k) (*qvs)[k].assign(q.begin() + rPosStart_[k], q.begin() + rPosStart_[k + 1]);
     if (rich) {

@@ -267,11 +267,28 @@ void ckpt_policy(int* K, int* minLen);
 // stream, the lane-serial fill) its batched middle-case scoring and the repeat rounds' multi-base scoring (cells = tasks).
 // kKScoreWide: Arrow's scoring of mutations of any width (k_score_wide and k_score_wide_refill; cells = tasks).
 // kKQvRich: k_qv_rich, the QV kernel of a rich-QV call, apart from kKQv's k_qv.
+// kKStrandSums / kKStrandSites: the strand-discordance screen's two kernels.
 enum KernelKind {
     kKFill = 0, kKSuffix, kKEnumerate, kKScore, kKReduce, kKQv, kKSelect, kKCompact, kKFillTall,
-    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKScoreWide, kKQvRich, kKernelKinds
+    kKQFillGrp, kKQFillCoop, kKQFillLane, kKQScoreMid, kKQScoreMulti, kKScoreWide, kKQvRich, kKStrandSums,
+    kKStrandSites, kKernelKinds
 };
 extern const char* const kKernelNames[kKernelKinds];
+
+// The strand-discordance screen (strand_kernels.hpp states the rules).
+struct StrandOptions {
+    double minScore = 12.5;   // T: one strand's sum above T, the other's below -T
+    int minReads = 2;         // reads of each strand that score the mutation
+};
+struct StrandSiteH {
+    int pos = 0, type = 0;
+    char base = '-';          // '-' for a deletion
+    double sumF = 0.0, sumR = 0.0;
+};
+struct StrandSumsH {          // per listed mutation
+    std::vector<double> sumF, sumR;
+    std::vector<int> nF, nR;
+};
 
 struct KernelStat {
     long long launches = 0;
@@ -377,7 +394,9 @@ public:
     // per listed ZMW (empty for the ones that do not converge); with reclaim on, their bands are then dropped.
     void Refine(const std::vector<int>& zmws, const RefineOptions& ro, std::vector<int>* converged,
                 std::vector<long long>* nTested, std::vector<long long>* nApplied, bool needFinalState = true,
-                std::vector<std::vector<int>>* qvsOnConverge = nullptr, std::vector<RichQVs>* richOnConverge = nullptr);
+                std::vector<std::vector<int>>* qvsOnConverge = nullptr, std::vector<RichQVs>* richOnConverge = nullptr,
+                const StrandOptions* strand = nullptr,
+                std::vector<std::vector<StrandSiteH>>* strandOnConverge = nullptr);
     // Band reclaim (batch polish): a fill whose list holds every read with live bands lays the value pool out
     // afresh from offset 0, each region sized from the read's last band.  Live = filled, active
     // and not retired; the caller retires the ZMWs whose bands it will not read again.
@@ -393,7 +412,13 @@ public:
     void Retire(const std::vector<int>& zmws);
     // ConsensusQVs for the listed ZMWs.  rich != nullptr: the same sweep, then k_qv_rich instead of k_qv: the same
     // qvs and the per-type QVs and tags of every position.
-    void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich = nullptr);
+    // strand != nullptr: k_strand_sums and k_strand_sites after the QV kernel, on the same round's deltas; sites
+    // receives each listed ZMW's discordant positions in template order.
+    void QVs(const std::vector<int>& zmws, std::vector<std::vector<int>>* qvs, std::vector<RichQVs>* rich = nullptr,
+             const StrandOptions* strand = nullptr, std::vector<std::vector<StrandSiteH>>* sites = nullptr);
+    // The per-strand sums of an explicit single-base mutation list: one scoring round without a fast-score break,
+    // then k_strand_sums.
+    void StrandScores(int z, const std::vector<int>& codes, StrandSumsH* out);
     // ApplyMutations (MultiReadMutationScorer.cpp:235-267).  Returns false on an invalid edit.
     bool ApplyMutations(int z, const std::vector<Mutation>& muts);
     // ---- mutations of any width (k_score_wide) -------------------------------------------
@@ -593,6 +618,8 @@ private:
     DevVec<WideTask> dWide_;     // the task list of k_score_wide and k_score_wide_refill and its deltas (ScoreWide)
     DevVec<double> dWideDelta_;
     DevVec<int> dRich_;          // k_qv_rich's three QV arrays and, behind them, its two tag arrays
+    DevVec<double> dStrandD_;    // k_strand_sums' two sums per mutation, then k_strand_sites' two per position
+    DevVec<int> dStrandI_;       // ... their counts per mutation, then the flag and code per position
     int wideRows_ = 64;          // band values per column a refill of k_score_wide_refill may take (grown on overflow)
     DiploidScratch diploid_;
     struct Pending {

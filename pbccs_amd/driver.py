@@ -185,7 +185,7 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
-              polish_window=None, rich_qvs=False, kinetics=False):
+              polish_window=None, rich_qvs=False, kinetics=False, strand_sites=False, directional=None):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -209,6 +209,9 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     (CodecV1 codes), the same names with _mean and _cov, fn and rn -- from its final consensus and those subreads,
     whole and with their "ip" / "pw" tracks, whose add_read_results entry is SUCCESS.  A chunk whose reads carry
     no tracks raises before any device work.
+    strand_sites / directional (pbccs_ccs_batch_strand): as polish_zmws' keywords -- the results also
+    carry strand_sites and, for the ZMWs polished once more per strand, the "fwd" and "rev" sub-records, their
+    add_read_results / zscores indexed by input subread like the joint record's.  Not with polish_window (ValueError).
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -219,6 +222,14 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     from . import lib as L
     from .polish import ConsensusSettings
     from .quiver import _struct_dtype
+    strand = None
+    if directional is None and settings is not None:
+        directional = getattr(settings, "directional", None)
+    if strand_sites or directional is not None:
+        if polish_window is not None:
+            raise ValueError("the strand screen and the directional polish do not run on the windowed polish")
+        from .strand import strand_options
+        strand = strand_options(strand_sites, directional)
     if kinetics:   # before any engine is touched
         for z, c in enumerate(chunks):
             if c["reads"] and not any(r.get("ip") is not None or r.get("pw") is not None for r in c["reads"]):
@@ -275,6 +286,7 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     mc = 2**62 if max_poa_coverage is None else int(max_poa_coverage)
     winfo = None
     rich = None
+    sb = None
     if rich_qvs:   # one pbccs_rich_qvs per ZMW over shared arrays laid out like qv
         total = max(1, int(cstart[-1]))
         rich_qv = np.zeros((3, total), dtype=np.int32)
@@ -288,6 +300,17 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
             rich["cap"][:n] = caps
         x = L.CPolishExtras()
         x.rich = ctypes.cast(rich.ctypes.data, ctypes.POINTER(L.CRichQvs))
+    if strand is not None:
+        from .strand import SiteBuffers
+        x = x if rich_qvs else L.CPolishExtras()
+        sb = SiteBuffers(caps.tolist(), counts.tolist())
+        co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
+        po = L.CPoaOptions(mc, -1, 1 if banded_poa else 0)
+        L.check(L.load().pbccs_ccs_batch_strand(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                                ctypes.byref(co), ctypes.byref(po), ctypes.byref(opts), ctypes.byref(x),
+                                                ctypes.byref(strand), sb.arr,
+                                                ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    elif rich_qvs:
         wo = None
         if polish_window is not None:
             from .polish import window_options
@@ -355,6 +378,9 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
             res[-1].update(sub_qv=rich_qv[0, c:c + rl].tolist(), ins_qv=rich_qv[1, c:c + rl].tolist(),
                            del_qv=rich_qv[2, c:c + rl].tolist(), sub_tag=rich_tag[0, c:c + rl].tobytes().decode(),
                            ins_tag=rich_tag[1, c:c + rl].tobytes().decode())
+        if sb is not None:
+            res[-1]["strand_sites"] = sb.sites(z)
+            res[-1].update(sb.sub_records(z))
     if kinetics:
         from .kinetics import kinetics_batch
         todo = [z for z in range(n) if res[z]["status_code"] in (0, 6) and res[z]["consensus"]]

@@ -280,6 +280,23 @@ class CPolishExtras(ctypes.Structure):
                 ("repeat_applied", ctypes.POINTER(ctypes.c_longlong)), ("rich", ctypes.POINTER(CRichQvs))]
 
 
+class CStrandOptions(ctypes.Structure):
+    _fields_ = [("min_score", ctypes.c_double), ("min_reads", ctypes.c_int), ("min_sites", ctypes.c_int),
+                ("directional", ctypes.c_int)]
+
+
+class CStrandResult(ctypes.Structure):
+    _fields_ = [("n_sites", ctypes.c_int), ("cap", ctypes.c_int), ("position", ctypes.POINTER(ctypes.c_int)),
+                ("type", ctypes.POINTER(ctypes.c_int)), ("base", ctypes.POINTER(ctypes.c_char)),
+                ("sum_fwd", ctypes.POINTER(ctypes.c_double)), ("sum_rev", ctypes.POINTER(ctypes.c_double)),
+                ("split", ctypes.c_int), ("fwd", CZmwOutput), ("rev", CZmwOutput)]
+
+
+class CStrandStats(ctypes.Structure):
+    _fields_ = [("strand_screened", ctypes.c_longlong), ("strand_sites", ctypes.c_longlong),
+                ("strand_split", ctypes.c_longlong)]
+
+
 class CKineticsRead(ctypes.Structure):
     _fields_ = [("transcript", ctypes.c_char_p), ("transcript_len", ctypes.c_int), ("rc", ctypes.c_int),
                 ("rb", ctypes.c_int), ("tb", ctypes.c_int), ("te", ctypes.c_int), ("len", ctypes.c_int),
@@ -472,6 +489,19 @@ SIGNATURES = {
     "pbccs_polish_windowed_ex": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
                                      ctypes.POINTER(CWindowOptions), ctypes.POINTER(CPolishExtras),
                                      ctypes.POINTER(CZmwOutput), ctypes.POINTER(CWindowInfo)]),
+    # directional consensus
+    "pbccs_strand_options_default": (None, [ctypes.POINTER(CStrandOptions)]),
+    "pbccs_polish_batch_strand": (I, [P, ctypes.POINTER(CZmwInput), I, ctypes.POINTER(CPolishOptions),
+                                      ctypes.POINTER(CPolishExtras), ctypes.POINTER(CStrandOptions),
+                                      ctypes.POINTER(CStrandResult), ctypes.POINTER(CZmwOutput)]),
+    "pbccs_ccs_batch_strand": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                                   ctypes.POINTER(CPoaOptions), ctypes.POINTER(CPolishOptions),
+                                   ctypes.POINTER(CPolishExtras), ctypes.POINTER(CStrandOptions),
+                                   ctypes.POINTER(CStrandResult), ctypes.POINTER(CCcsOutput)]),
+    "pbccs_scorer_strand_scores": (I, [P, PM, I, PD, PD, PI, PI]),
+    "pbccs_scorer_strand_sites": (I, [P, ctypes.POINTER(CStrandOptions), PI, PI, ctypes.POINTER(ctypes.c_char), PD,
+                                      PD, I, PI]),
+    "pbccs_strand_stats_get": (I, [P, ctypes.POINTER(CStrandStats), I]),
     # consensus kinetics
     "pbccs_kinetics_options_default": (None, [ctypes.POINTER(CKineticsOptions)]),
     "pbccs_kinetics_pileup": (I, [P, ctypes.POINTER(CKineticsPileupInput), I, ctypes.POINTER(CKineticsOutput)]),

@@ -15,7 +15,7 @@ class ConsensusSettings:
 
     def __init__(self, min_passes=3, min_length=10, min_zscore=-5.0, max_drop_fraction=0.34,
                  min_predicted_accuracy=0.90, score_diff=12.5, max_iterations=40, mutation_separation=10,
-                 mutation_neighborhood=20, zmws_per_batch=0):
+                 mutation_neighborhood=20, zmws_per_batch=0, directional=None):
         self.min_passes = min_passes
         self.min_length = min_length
         self.min_zscore = min_zscore
@@ -26,6 +26,10 @@ class ConsensusSettings:
         self.mutation_separation = mutation_separation
         self.mutation_neighborhood = mutation_neighborhood
         self.zmws_per_batch = zmws_per_batch
+        # ConsensusSettings::Directional (Consensus.h:94; the reference's option is commented out): None,
+        # "discordant" or "always" -- what polish_zmws / polish_stream / driver.ccs_batch do when their own
+        # `directional` keyword is not given
+        self.directional = directional
 
     def _c(self):
         o = L.CPolishOptions()
@@ -159,10 +163,11 @@ def _add_rich(res, rb):
     return res
 
 
-def _polish_repeats(zmws, settings, engine, repeats, one_batch, rich_qvs=False):
+def _polish_repeats(zmws, settings, engine, repeats, one_batch, rich_qvs=False, strand=None):
     """pbccs_polish_batch_ex: RefineConsensus, RefineRepeats(repeat_length, min_repeat_elements), ConsensusQVs per
     ZMW; the records gain n_repeat_tested / n_repeat_applied.  rich_qvs (with or without
-    repeats): pbccs_polish_batch_ex2 with one pbccs_rich_qvs per ZMW."""
+    repeats): pbccs_polish_batch_ex2 with one pbccs_rich_qvs per ZMW.  strand (a pbccs_strand_options):
+    pbccs_polish_batch_strand; the records gain strand_sites and, when split, fwd / rev."""
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
@@ -177,7 +182,20 @@ def _polish_repeats(zmws, settings, engine, repeats, one_batch, rich_qvs=False):
         ro = L.CRepeatOptions(int(repeat_length), int(min_repeat_elements), 1, 10, 20)
         rt = (ctypes.c_longlong * max(1, n))()
         ra = (ctypes.c_longlong * max(1, n))()
-    if rich_qvs:
+    if strand is not None:
+        from .strand import SiteBuffers
+        x = L.CPolishExtras()
+        if rich_qvs:
+            rb = _rich_buffers(m)
+            x = rb.extras(ro, rt, ra)
+        elif ro is not None:
+            x.repeats = ctypes.pointer(ro)
+            x.repeat_tested = rt
+            x.repeat_applied = ra
+        sb = SiteBuffers([o.consensus_cap for o in m._outs[:n]], [len(z["reads"]) for z in zmws])
+        L.check(L.load().pbccs_polish_batch_strand(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(x),
+                                                   ctypes.byref(strand), sb.arr, m._outs))
+    elif rich_qvs:
         rb = _rich_buffers(m)
         x = rb.extras(ro, rt, ra)
         L.check(L.load().pbccs_polish_batch_ex2(engine._h, m._ins, n, ctypes.byref(opts), ctypes.byref(x), m._outs))
@@ -189,10 +207,25 @@ def _polish_repeats(zmws, settings, engine, repeats, one_batch, rich_qvs=False):
         for i, r in enumerate(res):
             r["n_repeat_tested"] = rt[i]
             r["n_repeat_applied"] = ra[i]
+    if strand is not None:
+        for i, r in enumerate(res):
+            r["strand_sites"] = sb.sites(i)
+            r.update(sb.sub_records(i))
     return _add_rich(res, rb) if rich_qvs else res
 
 
-def polish_zmws(zmws, settings=None, engine=None, repeats=None, rich_qvs=False):
+def _strand_keywords(strand_sites, directional, settings=None):
+    """The pbccs_strand_options of the batch keywords, or None when neither is given (settings.directional stands
+    in for a `directional` that is not given)."""
+    if directional is None and settings is not None:
+        directional = getattr(settings, "directional", None)
+    if not strand_sites and directional is None:
+        return None
+    from .strand import strand_options
+    return strand_options(strand_sites, directional)
+
+
+def polish_zmws(zmws, settings=None, engine=None, repeats=None, rich_qvs=False, strand_sites=False, directional=None):
     """Polish ZMWs on the GPU (upload, hot path, download).
 
     zmws: list of dicts {draft, snr (4), reads: [{seq, strand, ts, te, full_pass?}]}.
@@ -202,9 +235,16 @@ def polish_zmws(zmws, settings=None, engine=None, repeats=None, rich_qvs=False):
     (pbccs_polish_batch_ex); the records then also hold n_repeat_tested and n_repeat_applied.
     rich_qvs=True: the records also hold sub_qv, ins_qv, del_qv, sub_tag and ins_tag, the per-base rich QVs of the
     final template (pbccs_polish_batch_ex2; named by mutation type, see pbccs_amd.richqv).
+    strand_sites=True (or a dict with any of min_score, min_reads, min_sites): the records also hold strand_sites,
+    the StrandSite(pos, type, base, sum_fwd, sum_rev) list of the strand-discordance screen on the final template
+    (pbccs_polish_batch_strand).  directional="discordant" | "always": the ZMWs with sites / all
+    ZMWs are polished once more per strand, and their records hold "fwd" and "rev" sub-records, each what this
+    call returns for the ZMW with only that strand's reads (per-read entries indexed like the joint record's, -1 /
+    NaN for the other strand's reads).  Every other field is what the call without the keywords returns.
     """
-    if repeats is not None or rich_qvs:
-        return _polish_repeats(zmws, settings, engine, repeats, True, rich_qvs)
+    strand = _strand_keywords(strand_sites, directional, settings)
+    if repeats is not None or rich_qvs or strand is not None:
+        return _polish_repeats(zmws, settings, engine, repeats, True, rich_qvs, strand)
     b = PreparedBatch(zmws, settings, engine)
     try:
         b.polish()
@@ -279,7 +319,8 @@ def window_slices(zmws, window=2000, overlap=200, k=6, min_length=10, engine=Non
     return out
 
 
-def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6, engine=None, rich_qvs=False):
+def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6, engine=None, rich_qvs=False,
+                    strand_sites=False, directional=None):
     """Polish ZMWs with long drafts as overlapping windows (pbccs_polish_windowed).
 
     Results as polish_zmws plus "windowed" (the draft had more than one window), "fallback" (0, or the reason code
@@ -287,7 +328,10 @@ def polish_windowed(zmws, settings=None, window=2000, overlap=200, guard=8, k=6,
     begin, end, join (the draft position it is joined to the next window at, -1 for none), cut_begin / cut_end
     (its piece of its own consensus), status, n_tested, n_applied.
     rich_qvs=True: the five rich keys too (pbccs_polish_windowed_ex); the stitched arrays are the same pieces of the
-    windows' arrays as the stitched qvs."""
+    windows' arrays as the stitched qvs.
+    strand_sites / directional: not supported on windows; ValueError when given."""
+    if strand_sites or directional is not None:
+        raise ValueError("the strand screen and the directional polish do not run on the windowed polish")
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
@@ -351,13 +395,15 @@ def plan_batches(zmws, budget_bytes, max_per_batch=2000, max_len_ratio=1.5):
     return [list(order[start[b]:start[b + 1]]) for b in range(nb.value)], list(est[:n])
 
 
-def polish_stream(zmws, settings=None, engine=None, repeats=None, rich_qvs=False):
+def polish_stream(zmws, settings=None, engine=None, repeats=None, rich_qvs=False, strand_sites=False,
+                  directional=None):
     """Polish a stream of heterogeneous ZMWs (pbccs_polish_batch): bucketed by length and pass count into
     memory-sized device batches that the engine's workspace slots pull largest-first from one queue, like
-    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws(); `repeats` and
-    `rich_qvs` as there."""
-    if repeats is not None or rich_qvs:
-        return _polish_repeats(zmws, settings, engine, repeats, False, rich_qvs)
+    ccs's ZMW work queue (src/main/ccs.cpp:222-262).  Results in input order, as polish_zmws(); `repeats`,
+    `rich_qvs`, `strand_sites` and `directional` as there."""
+    strand = _strand_keywords(strand_sites, directional, settings)
+    if repeats is not None or rich_qvs or strand is not None:
+        return _polish_repeats(zmws, settings, engine, repeats, False, rich_qvs, strand)
     from . import default_engine
     engine = engine or default_engine()
     settings = settings or ConsensusSettings()
