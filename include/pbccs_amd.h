@@ -1240,6 +1240,105 @@ typedef struct {
 } pbccs_kinetics_stats;
 int pbccs_kinetics_stats_get(pbccs_engine* eng, pbccs_kinetics_stats* out, int reset);
 
+/* ---- subread pileup on the consensus: base counts, ec, gapped rows --------------------
+ * An opt-in with no counterpart in the reference; csrc/pileup_kernels.hpp states the rules.  Reads are placed and
+ * vetted as the kinetics calls place and vet them, with the same PBCCS_KIN_* statuses; only PBCCS_KIN_USED reads
+ * count.  Every array is indexed by consensus position, or by slot (slot s lies before position s, slot
+ * consensus_len after the last one), in the consensus's own direction for both strands -- unlike the kinetics
+ * arrays.  Strand 0 holds the rc == 0 reads, strand 1 the rc != 0 reads; codes are A C G T gap other = 0..5, a
+ * read character outside ACGT being "other" in either orientation (its complement is N). */
+typedef struct {
+    const char* transcript;   /* M R I D */
+    int transcript_len;
+    int rc, rb, tb, te;
+    const char* seq;          /* the read as sequenced, len characters */
+    int len;
+} pbccs_pileup_read;
+
+typedef struct {
+    const char* consensus;
+    int consensus_len;
+    int n_reads;
+    const pbccs_pileup_read* reads;
+} pbccs_pileup_columns_input;
+
+/* Every pointer may be NULL.  With L = consensus_len: counts [2][L][6]; ins_reads, ins_bases [2][L + 1] (reads
+ * with an insertion at the slot, and their inserted bases); slot_cov, max_ins, ins_plurality [L + 1]; cov,
+ * plurality [L] (the code with the largest count of both strands among A C G T gap, a tie going to the
+ * consensus's own base, else to the lowest code; 255 without coverage); ins_plurality[s] = 2 * inserting reads >
+ * slot_cov[s].  Per read (n_reads entries each): the status, the transcript's column counts (0 for a read that is
+ * not used) and the placement; re = rb + the read columns of the transcript.  transcripts / transcript_lens are
+ * written by pbccs_pileup_batch only: n_reads pointers, each NULL or a buffer of consensus_len + lens[r] bytes
+ * that receives the read's transcript (no terminator), and its length (0 for a read that is not used). */
+typedef struct {
+    int* counts;
+    int* ins_reads;
+    int* ins_bases;
+    int* slot_cov;
+    int* max_ins;
+    int* cov;
+    unsigned char* plurality;
+    unsigned char* ins_plurality;
+    int* read_status;
+    int* n_match;
+    int* n_mismatch;
+    int* n_ins;
+    int* n_del;
+    int* rc;
+    int* rb;
+    int* re;
+    int* tb;
+    int* te;
+    char* const* transcripts;
+    int* transcript_lens;
+    long long cov_sum;   /* the sum of cov; ec = cov_sum / consensus_len */
+    int n_used[2];
+} pbccs_pileup_output;
+
+/* k_pile_columns and k_pile_reduce on the caller's transcripts.  Refuses, with PBCCS_EINVAL before any device
+ * work, what pbccs_kinetics_pileup refuses. */
+int pbccs_pileup_columns(pbccs_engine* eng, const pbccs_pileup_columns_input* in, int n, pbccs_pileup_output* out);
+
+typedef struct {
+    const char* consensus;
+    int consensus_len;
+    int n_reads;
+    const char* const* seqs;              /* a NULL or zero-length read is PBCCS_KIN_UNMAPPED */
+    const int* lens;
+    const unsigned short* const* ip;      /* read only with `kinetics`: as pbccs_kinetics_input's */
+    const unsigned short* const* pw;
+    pbccs_kinetics_output* kinetics;      /* NULL, or where this ZMW's consensus kinetics go: the placement and
+                                             alignment stage then runs once for both features */
+} pbccs_pileup_input;
+
+typedef struct {
+    pbccs_align_band band;   /* passed to the aligner; PBCCS_BAND_OFF by default */
+} pbccs_pileup_options;
+void pbccs_pileup_options_default(pbccs_pileup_options* o);
+
+/* pbccs_kinetics_batch's placement and alignment stage (the same band option, the same refusals), then the pileup;
+ * also the kinetics of the ZMWs whose input names a kinetics output. */
+int pbccs_pileup_batch(pbccs_engine* eng, const pbccs_pileup_input* in, int n, const pbccs_pileup_options* opts,
+                       pbccs_pileup_output* out);
+
+/* The gapped rows on the caller's transcripts (k_pile_scan, k_pile_rows).  widths[z] receives the row width, L + the
+ * sum of max_ins; cols (NULL, or n pointers, each NULL or L ints) receives col[p], the cell of position p.  rows
+ * NULL: the widths (and cols) only, to size the buffers.  Otherwise rows holds n pointers, each NULL or n_reads *
+ * widths[z] bytes, with widths[z] on entry the width the buffer was sized for (PBCCS_EINVAL when it is not this
+ * call's): one row per read in input order, blank for a read that is not used. */
+int pbccs_pileup_msa(pbccs_engine* eng, const pbccs_pileup_columns_input* in, int n, int* widths, int* const* cols,
+                     char* const* rows);
+
+/* Pileup work since the last reset: reads given, reads skipped by reason, transcript columns walked, (ZMW, slot)
+ * threads of the reduction, kernel launches, reads sent through pbccs_pileup_batch's placement and alignment
+ * stage and how many of those also fed a kinetics output, device ms per kernel (profiling on). */
+typedef struct {
+    long long reads, skipped_unmapped, skipped_empty_extent, skipped_align_failed, columns, slots, launches;
+    long long placed, shared;
+    double columns_ms, reduce_ms, scan_ms, rows_ms;
+} pbccs_pileup_stats;
+int pbccs_pileup_stats_get(pbccs_engine* eng, pbccs_pileup_stats* out, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@ with zlib:
   ccs.cpp:402-475 takes them from pbbam's BamRecord;
 - `write_ccs_bam(path, movies, records)`: ccsio.ccs_sam_record lines (ccs.cpp:105-172's fields and tag
   order, Bin 0, MAPQ 255, flag 4) as BAM.
+- `write_aligned_bam(path, header_text, references, records)` / `read_aligned_bam(path)`: aligned records
+  (ccsio.subread_alignment_sam_record: subreads aligned to their own CCS read) with the
+  reference dictionary, `refID`, CIGAR words and the bin of the alignment's interval; the unaligned functions
+  above are unchanged.
 
 BAM parity is unpinned: no reference test holds a BAM file.  The tests check round trips and the byte
 layout against the specification (tests/test_bamio.py).
@@ -260,6 +264,129 @@ def read_bam(path):
     return header, lines
 
 
+# ------------------------------------------------------------------------------------- aligned records
+_CIGAR_OPS = "MIDNSHP=X"
+_CIGAR_REF = "MDN=X"       # operations that consume the reference
+
+
+def _parse_cigar(text):
+    """`12=1X3I` -> [(12, 7), (1, 8), (3, 1)] (length, operation code)."""
+    ops, n = [], ""
+    for ch in text:
+        if ch.isdigit():
+            n += ch
+            continue
+        if ch not in _CIGAR_OPS or not n:
+            raise ValueError(f"bad CIGAR {text!r}")
+        ops.append((int(n), _CIGAR_OPS.index(ch)))
+        n = ""
+    if n or not ops:
+        raise ValueError(f"bad CIGAR {text!r}")
+    return ops
+
+
+def aligned_sam_to_bam_record(line, ref_index):
+    """One aligned SAM text line -> the BAM record bytes including block_size (SAMv1 §4.2): refID from ref_index
+    (RNAME -> index in the header's reference dictionary), the CIGAR as length << 4 | operation words, and the bin
+    of [POS, the alignment's end) by reg2bin."""
+    f = line.rstrip("\n").split("\t")
+    qname, flag, rname, pos, mapq, cigar, rnext, pnext, tlen, seq, qual = f[:11]
+    if rname not in ref_index:
+        raise ValueError(f"RNAME {rname!r} is not in the reference dictionary")
+    ops = _parse_cigar(cigar)
+    if len(ops) > 0xffff:
+        raise ValueError("more than 65535 CIGAR operations")
+    seq = "" if seq == "*" else seq
+    lseq = len(seq)
+    if sum(n for n, op in ops if _CIGAR_OPS[op] in "MIS=X") != lseq:
+        raise ValueError("the CIGAR does not consume SEQ")
+    packed = bytearray((lseq + 1) // 2)
+    for i, c in enumerate(seq):
+        packed[i >> 1] |= _SEQ_INDEX.get(c.upper(), 15) << (4 if i % 2 == 0 else 0)
+    qb = bytes([0xff] * lseq) if qual == "*" else bytes(ord(c) - 33 for c in qual)
+    if len(qb) != lseq:
+        raise ValueError("QUAL length differs from SEQ length")
+    name = qname.encode() + b"\0"
+    p = int(pos) - 1
+    end = p + max(1, sum(n for n, op in ops if _CIGAR_OPS[op] in _CIGAR_REF))
+    nref = -1 if rnext == "*" else (ref_index[rname] if rnext == "=" else ref_index[rnext])
+    core = struct.pack("<iiBBHHHIiii", ref_index[rname], p, len(name), int(mapq), _reg2bin(p, end), len(ops),
+                       int(flag), lseq, nref, int(pnext) - 1, int(tlen))
+    body = core + name + b"".join(struct.pack("<I", n << 4 | op) for n, op in ops) + bytes(packed) + qb + \
+        b"".join(_encode_tag(t) for t in f[11:])
+    return struct.pack("<i", len(body)) + body
+
+
+def aligned_bam_record_to_sam(rec, names):
+    """BAM record bytes (without block_size) -> the SAM text line; names: the reference dictionary's names."""
+    (ref, pos, lname, mapq, _bin, ncig, flag, lseq, nref, npos, tlen) = struct.unpack_from("<iiBBHHHIiii", rec, 0)
+    k = 32
+    name = rec[k:k + lname - 1].decode()
+    k += lname
+    cigar = "".join(f"{w >> 4}{_CIGAR_OPS[w & 15]}" for w in struct.unpack_from("<%dI" % ncig, rec, k)) or "*"
+    k += 4 * ncig
+    seq = "".join(_SEQ_CODES[(rec[k + (i >> 1)] >> (4 if i % 2 == 0 else 0)) & 15] for i in range(lseq))
+    k += (lseq + 1) // 2
+    q = rec[k:k + lseq]
+    k += lseq
+    qual = "*" if lseq == 0 or all(b == 0xff for b in q) else "".join(chr(b + 33) for b in q)
+    rnext = "*" if nref < 0 else ("=" if nref == ref else names[nref])
+    fields = [name, str(flag), "*" if ref < 0 else names[ref], str(pos + 1), str(mapq), cigar, rnext, str(npos + 1),
+              str(tlen), seq or "*", qual]
+    return "\t".join(fields + _decode_tags(rec, k))
+
+
+def write_aligned_bam(path, header_text, references, sam_lines):
+    """An aligned BAM: header_text, the reference dictionary references = [(name, length)] and aligned SAM text
+    lines (ccsio.subread_alignment_sam_record's), each RNAME one of the references.  Returns each record's BGZF
+    virtual offset.  No index is written."""
+    references = [(str(nm), int(ln)) for nm, ln in references]
+    index = {}
+    for nm, _ in references:
+        if nm in index:
+            raise ValueError(f"reference {nm!r} twice")
+        index[nm] = len(index)
+    offsets = []
+    with BgzfWriter(path) as w:
+        ht = header_text.encode()
+        head = b"BAM\1" + struct.pack("<i", len(ht)) + ht + struct.pack("<i", len(references))
+        for nm, ln in references:
+            b = nm.encode() + b"\0"
+            head += struct.pack("<i", len(b)) + b + struct.pack("<i", ln)
+        w.write(head)
+        for line in sam_lines:
+            offsets.append(w.tell())
+            w.write(aligned_sam_to_bam_record(line, index))
+    return offsets
+
+
+def read_aligned_bam(path):
+    """(header_text, [(name, length)], [SAM text lines]) of a BAM written by write_aligned_bam."""
+    r = BgzfReader(path)
+    data = r.read_all()
+    r.close()
+    if data[:4] != b"BAM\1":
+        raise ValueError("not a BAM file")
+    lt = struct.unpack_from("<i", data, 4)[0]
+    header = data[8:8 + lt].decode().rstrip("\0")
+    k = 8 + lt
+    nref = struct.unpack_from("<i", data, k)[0]
+    k += 4
+    refs = []
+    for _ in range(nref):
+        ln = struct.unpack_from("<i", data, k)[0]
+        nm = data[k + 4:k + 4 + ln - 1].decode()
+        refs.append((nm, struct.unpack_from("<i", data, k + 4 + ln)[0]))
+        k += 4 + ln + 4
+    names = [nm for nm, _ in refs]
+    lines = []
+    while k < len(data):
+        bs = struct.unpack_from("<i", data, k)[0]
+        lines.append(aligned_bam_record_to_sam(data[k + 4:k + 4 + bs], names))
+        k += 4 + bs
+    return header, refs, lines
+
+
 # ---------------------------------------------------------------------------------------- ccs front/back
 def _tag_dict(tags):
     d = {}
@@ -361,5 +488,6 @@ def subread_sam_line(movie, hole, qs, qe, seq, snr, flags=3, read_score=0.9, rg=
     return "\t".join([f"{movie}/{hole}/{qs}_{qe}", "4", "*", "0", "255", "*", "*", "0", "0", seq, "*"] + tags)
 
 
-__all__ = ["BgzfReader", "BgzfWriter", "bam_record_to_sam", "group_subread_bam", "read_bam", "read_subread_bam",
-           "sam_to_bam_record", "subread_sam_line", "write_bam", "write_ccs_bam"]
+__all__ = ["BgzfReader", "BgzfWriter", "aligned_bam_record_to_sam", "aligned_sam_to_bam_record", "bam_record_to_sam",
+           "group_subread_bam", "read_aligned_bam", "read_bam", "read_subread_bam", "sam_to_bam_record",
+           "subread_sam_line", "write_aligned_bam", "write_bam", "write_ccs_bam"]

@@ -148,7 +148,7 @@ def _ccs_name(movie, hole, strand):
     return f"{movie}/{hole}/ccs/{strand}"
 
 
-def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=None):
+def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=None, pileup=False):
     """The CCS record of src/main/ccs.cpp:105-172 as a SAM text line (unmapped, flag 4; MAPQ 255).
 
     result: one pbccs_amd polish result (status Success).  Tags in the reference's order: RG zm np rq sn pq
@@ -162,6 +162,8 @@ def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=
     same for the reverse strand, in the reverse strand's direction) and rn.
     strand="fwd" | "rev" (result: the "fwd" / "rev" sub-record of a directional polish): the record
     is named movie/hole/ccs/fwd or .../ccs/rev.
+    pileup=True (a result made with pileup=True): the effective coverage follows every other tag as ec:f: (the sum
+    over the consensus of the subread columns standing on each position, over its length).
     """
     name = _ccs_name(movie, hole, strand)
     qual = QVsToASCII(result["qvs"])
@@ -186,7 +188,31 @@ def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=
             return f"{tag}:B:C" + "".join(f",{int(c)}" for c in result[key])
         tags += [codes("fi", "fwd_ipd"), codes("fp", "fwd_pw"), f"fn:i:{int(result['fn'])}",
                  codes("ri", "rev_ipd"), codes("rp", "rev_pw"), f"rn:i:{int(result['rn'])}"]
+    if pileup:
+        tags.append(f"ec:f:{_f32(result['ec'])}")
     fields =[name, "4", "*", "0", "255", "*", "*", "0", "0", result["consensus"] or "*", qual or "*"]
+    return "\t".join(fields + tags)
+
+
+_COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+def subread_alignment_sam_record(ccs_name, subread_name, seq, read):
+    """One subread aligned to its own CCS read, as a SAM text line.  seq: the subread as
+    sequenced; read: its entry of a pileup made with transcripts=True ("status" used; "transcript", "rc", "rb", "tb",
+    the column counts and "concordance").  FLAG 16 for a reverse-complemented read, else 0; RNAME ccs_name; POS
+    tb + 1; MAPQ 255; the CIGAR of pileup.cigar (= X I D and S clips); SEQ the oriented read (the reverse complement,
+    N for a character outside ACGT, when rc); QUAL *; NM:i: mismatches + inserted + deleted bases; mc:f: the
+    concordance."""
+    from .pileup import cigar
+    if read.get("status") != "used" or read.get("transcript") is None:
+        raise ValueError("subread_alignment_sam_record: a used read of a pileup made with transcripts=True")
+    rc = bool(read["rc"])
+    oriented = "".join(_COMPLEMENT.get(c, "N") for c in reversed(seq)) if rc else seq
+    tags = [f"NM:i:{int(read['n_mismatch']) + int(read['n_ins']) + int(read['n_del'])}",
+            f"mc:f:{_f32(read['concordance'])}"]
+    fields = [subread_name, "16" if rc else "0", ccs_name, str(int(read["tb"]) + 1), "255",
+              cigar(read["transcript"], read["rb"], len(seq)), "*", "0", "0", oriented or "*", "*"]
     return "\t".join(fields + tags)
 
 
@@ -216,4 +242,5 @@ def count_results(results, pre=None):
 
 
 __all__ = ["ADAPTER_AFTER", "ADAPTER_BEFORE", "ResultCounts", "ZMW_STATUS", "ccs_fastq_record", "ccs_sam_record",
-           "count_results", "group_zmws", "parse_subread_name", "read_fasta", "read_group_id", "sam_header"]
+           "count_results", "group_zmws", "parse_subread_name", "read_fasta", "read_group_id", "sam_header",
+           "subread_alignment_sam_record"]

@@ -27,6 +27,7 @@
 #include "engine.hpp"
 #include "driver.hpp"
 #include "kinetics_kernels.hpp"
+#include "pileup_kernels.hpp"
 #include "map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
@@ -138,6 +139,15 @@ struct pbccs_engine {
         if (!kineticsRunner) kineticsRunner.reset(new kinetics::KineticsRunner(device));
         kineticsRunner->profiling = profiling;
         return *kineticsRunner;
+    }
+    // the base pileup's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<pileup::PileupRunner> pileupRunner;
+    std::mutex pileupMu;
+    pileup::PileupRunner& Pileup()
+    {
+        if (!pileupRunner) pileupRunner.reset(new pileup::PileupRunner(device));
+        pileupRunner->profiling = profiling;
+        return *pileupRunner;
     }
     Workspace* Slot(int s)
     {
@@ -3127,14 +3137,29 @@ int pbccs_kinetics_pileup(pbccs_engine* eng, const pbccs_kinetics_pileup_input* 
 }
 
 namespace {
-// One slice of pbccs_kinetics_batch: ZMWs [z0, z1)
-void kinetics_slice(pbccs_engine* eng, const pbccs_kinetics_input* in, int z0, int z1,
-                    const pbccs_kinetics_options& opts, pbccs_kinetics_output* out)
+extern "C++" {   // templates inside the ABI's extern "C" block
+// The placement and alignment stage pbccs_kinetics_batch and pbccs_pileup_batch share, for the ZMWs [z0, z1) of an
+// input with consensus, consensus_len, n_reads, seqs and lens: pbccs_map_batch's placement, then Align (NW, default
+// parameters) of consensus[tb, te) against the oriented read's [rb, re).
+struct PlacedRead {
+    int rc, rb, re, tb, te;
+    int skip;         // kinetics::kUsed, or why the read is skipped
+    const char* tr;   // the transcript (owned by the stage), NULL for a skipped read
+    int trLen;
+};
+struct PlaceStage {
+    std::vector<std::vector<PlacedRead>> reads;   // per ZMW of the slice
+    std::vector<std::string> oriented;            // the reverse-complemented extents (the forward ones are views)
+    std::vector<align::PairResult> res;
+};
+
+template <class In>
+void place_and_align(pbccs_engine* eng, const In* in, int z0, int z1, const pbccs_align_band& band, PlaceStage& st)
 {
     const int n = z1 - z0;
     std::vector<map::MapGroup> groups((size_t)n);
     for (int g = 0; g < n; ++g) {
-        const pbccs_kinetics_input& m = in[z0 + g];
+        const In& m = in[z0 + g];
         groups[g] = map::MapGroup{m.consensus, m.consensus_len, m.seqs, m.lens, m.n_reads};
     }
     std::vector<map::MapResult> placed;
@@ -3143,25 +3168,24 @@ void kinetics_slice(pbccs_engine* eng, const pbccs_kinetics_input* in, int z0, i
         eng->Map().Run(groups.data(), n, 0.0f, &placed);
     }
     // the pairs: consensus[tb, te) against the oriented read's [rb, re)
-    std::vector<std::vector<kinetics::ReadView>> rv((size_t)n);
-    std::vector<std::string> oriented;   // the reverse-complemented extents (the forward ones are views)
+    st.reads.assign((size_t)n, {});
     std::vector<align::PairView> pairs;
     std::vector<std::pair<int, int>> pairOf;   // (ZMW of the slice, read)
     size_t idx = 0, nRev = 0;
     for (int g = 0; g < n; ++g)
         for (int r = 0; r < in[z0 + g].n_reads; ++r, ++idx)
             if (placed[idx].mapped && placed[idx].rc) ++nRev;
-    oriented.reserve(nRev);   // the pairs keep pointers into the strings
+    st.oriented.clear();
+    st.oriented.reserve(nRev);   // the pairs keep pointers into the strings
     idx = 0;
     for (int g = 0; g < n; ++g) {
-        const pbccs_kinetics_input& m = in[z0 + g];
-        rv[g].resize((size_t)m.n_reads);
+        const In& m = in[z0 + g];
+        st.reads[g].resize((size_t)m.n_reads);
         for (int r = 0; r < m.n_reads; ++r, ++idx) {
             const map::MapResult& p = placed[idx];
-            kinetics::ReadView& v = rv[g][r];
-            v = kinetics::ReadView{nullptr, 0, p.rc, p.ext[0], p.ext[2], p.ext[3], m.lens[r], m.ip ? m.ip[r] : nullptr,
-                                   m.pw ? m.pw[r] : nullptr, kinetics::kUsed};
+            PlacedRead& v = st.reads[g][r];
             const int rb = p.ext[0], re = p.ext[1], tb = p.ext[2], te = p.ext[3];
+            v = PlacedRead{p.rc, rb, re, tb, te, kinetics::kUsed, nullptr, 0};
             if (!p.mapped) {
                 v.skip = kinetics::kUnmapped;
                 continue;
@@ -3175,47 +3199,81 @@ void kinetics_slice(pbccs_engine* eng, const pbccs_kinetics_input* in, int z0, i
                 std::string s((size_t)(re - rb), ' ');
                 const int I = m.lens[r];
                 for (int k = rb; k < re; ++k) s[(size_t)(k - rb)] = kin_complement(m.seqs[r][I - 1 - k]);
-                oriented.push_back(std::move(s));
-                q = oriented.back().data();
+                st.oriented.push_back(std::move(s));
+                q = st.oriented.back().data();
             }
             pairs.push_back(align::PairView{m.consensus + tb, te - tb, q, re - rb});
             pairOf.emplace_back(g, r);
         }
     }
     const int np = (int)pairs.size();
-    std::vector<align::PairResult> res((size_t)np);
+    st.res.assign((size_t)np, align::PairResult());
     if (np) {
         const align::AlignScoring sc{PBCCS_ALIGN_NW, 0, -1, -1, -1, 0.f, 0.f, 0.f, 0.f, 0.f};   // AlignConfig::Default()
         std::lock_guard<std::mutex> lk(eng->alignMu);
-        if (opts.band.mode != PBCCS_BAND_OFF) {
+        if (band.mode != PBCCS_BAND_OFF) {
             align::BandOptions bo;
             bo.on = true;
-            bo.w = opts.band.mode == PBCCS_BAND_WIDTH ? opts.band.w : -1;
-            eng->Align().RunBanded(sc, pairs.data(), np, res.data(), bo, nullptr);
+            bo.w = band.mode == PBCCS_BAND_WIDTH ? band.w : -1;
+            eng->Align().RunBanded(sc, pairs.data(), np, st.res.data(), bo, nullptr);
         } else {
-            eng->Align().Run(sc, pairs.data(), np, res.data());
+            eng->Align().Run(sc, pairs.data(), np, st.res.data());
         }
     }
     for (int k = 0; k < np; ++k) {
-        kinetics::ReadView& v = rv[pairOf[k].first][pairOf[k].second];
-        if (res[k].status != PBCCS_OK) {
+        PlacedRead& v = st.reads[pairOf[k].first][pairOf[k].second];
+        if (st.res[k].status != PBCCS_OK) {
             v.skip = kinetics::kAlignFailed;
             continue;
         }
-        v.tr = res[k].transcript.data();
-        v.trLen = (int)res[k].transcript.size();
+        v.tr = st.res[k].transcript.data();
+        v.trLen = (int)st.res[k].transcript.size();
     }
-    std::vector<kinetics::ZmwView> zv((size_t)n);
-    std::vector<kinetics::ZmwOut> zo((size_t)n);
+}
+
+// The kinetics pileup of the stage's reads: ZMW g of the stage goes to outs[g] where that is not NULL
+template <class In>
+void kinetics_of_stage(pbccs_engine* eng, const In* in, int z0, const PlaceStage& st,
+                       const std::vector<pbccs_kinetics_output*>& outs)
+{
+    const int n = (int)st.reads.size();
+    std::vector<std::vector<kinetics::ReadView>> rv;
+    std::vector<kinetics::ZmwView> zv;
+    std::vector<kinetics::ZmwOut> zo;
+    std::vector<pbccs_kinetics_output*> dst;
+    rv.reserve((size_t)n);
     for (int g = 0; g < n; ++g) {
-        zv[g] = kinetics::ZmwView{in[z0 + g].consensus_len, rv[g].data(), in[z0 + g].n_reads};
-        zo[g] = kin_out_view(out[z0 + g]);
+        if (!outs[g]) continue;
+        const In& m = in[z0 + g];
+        rv.emplace_back((size_t)m.n_reads);
+        for (int r = 0; r < m.n_reads; ++r) {
+            const PlacedRead& p = st.reads[g][r];
+            rv.back()[r] = kinetics::ReadView{p.tr, p.trLen, p.rc, p.rb, p.tb, p.te, m.lens[r],
+                                              m.ip ? m.ip[r] : nullptr, m.pw ? m.pw[r] : nullptr, p.skip};
+        }
+        zv.push_back(kinetics::ZmwView{m.consensus_len, rv.back().data(), m.n_reads});
+        zo.push_back(kin_out_view(*outs[g]));
+        dst.push_back(outs[g]);
     }
+    if (zv.empty()) return;
     {
         std::lock_guard<std::mutex> lk(eng->kineticsMu);
-        eng->Kinetics().Run(zv.data(), n, zo.data());
+        eng->Kinetics().Run(zv.data(), (int)zv.size(), zo.data());
     }
-    kin_outputs(zo, n, out + z0);
+    for (size_t k = 0; k < dst.size(); ++k) kin_outputs({zo[k]}, 1, dst[k]);
+}
+
+}  // extern "C++"
+
+// One slice of pbccs_kinetics_batch: ZMWs [z0, z1)
+void kinetics_slice(pbccs_engine* eng, const pbccs_kinetics_input* in, int z0, int z1,
+                    const pbccs_kinetics_options& opts, pbccs_kinetics_output* out)
+{
+    PlaceStage st;
+    place_and_align(eng, in, z0, z1, opts.band, st);
+    std::vector<pbccs_kinetics_output*> outs((size_t)(z1 - z0));
+    for (int g = 0; g < z1 - z0; ++g) outs[g] = out + z0 + g;
+    kinetics_of_stage(eng, in, z0, st, outs);
 }
 }  // namespace
 
@@ -3271,6 +3329,240 @@ int pbccs_kinetics_stats_get(pbccs_engine* eng, pbccs_kinetics_stats* out, int r
         *out = pbccs_kinetics_stats{s.reads,     s.unmapped, s.emptyExtent, s.alignFailed, s.columns,
                                     s.positions, s.launches, s.columnsMs,   s.reduceMs};
         if (reset && eng->kineticsRunner) eng->kineticsRunner->stats = kinetics::KinStats();
+        return PBCCS_OK;
+    });
+}
+
+// ---- subread pileup (pileup_kernels.hpp) ---------------------------------------------------------------------
+namespace {
+pileup::ZmwOut pile_out_view(const pbccs_pileup_output& o)
+{
+    pileup::ZmwOut v;
+    v.counts = o.counts;
+    v.insReads = o.ins_reads;
+    v.insBases = o.ins_bases;
+    v.slotCov = o.slot_cov;
+    v.cov = o.cov;
+    v.maxIns = o.max_ins;
+    v.plurality = o.plurality;
+    v.insPlurality = o.ins_plurality;
+    v.readStatus = o.read_status;
+    v.nMatch = o.n_match;
+    v.nMismatch = o.n_mismatch;
+    v.nIns = o.n_ins;
+    v.nDel = o.n_del;
+    v.covSum = 0;
+    v.nUsed[0] = v.nUsed[1] = 0;
+    return v;
+}
+
+// the per-ZMW figures and the placement of n reads
+void pile_outputs(const pileup::ZmwOut& zo, const pileup::ZmwView& zv, pbccs_pileup_output& o)
+{
+    o.cov_sum = zo.covSum;
+    o.n_used[0] = zo.nUsed[0];
+    o.n_used[1] = zo.nUsed[1];
+    for (int k = 0; k < zv.n; ++k) {
+        const pileup::ReadView& r = zv.reads[k];
+        if (o.rc) o.rc[k] = r.rc ? 1 : 0;
+        if (o.rb) o.rb[k] = r.rb;
+        if (o.tb) o.tb[k] = r.tb;
+        if (o.te) o.te[k] = r.te;
+    }
+}
+
+bool bad_columns_input(const pbccs_pileup_columns_input* in, int n)
+{
+    for (int z = 0; z < n; ++z)
+        if (in[z].consensus_len < 0 || in[z].n_reads < 0 || (in[z].n_reads > 0 && !in[z].reads) ||
+            (in[z].consensus_len > 0 && !in[z].consensus))
+            return true;
+    return false;
+}
+
+void columns_views(const pbccs_pileup_columns_input* in, int n, std::vector<std::vector<pileup::ReadView>>& rv,
+                   std::vector<pileup::ZmwView>& zv)
+{
+    rv.assign((size_t)n, {});
+    zv.assign((size_t)n, pileup::ZmwView());
+    for (int z = 0; z < n; ++z) {
+        rv[z].resize((size_t)in[z].n_reads);
+        for (int k = 0; k < in[z].n_reads; ++k) {
+            const pbccs_pileup_read& r = in[z].reads[k];
+            rv[z][k] = pileup::ReadView{r.transcript, r.transcript_len, r.seq, r.len, r.rc, r.rb, r.tb, r.te,
+                                        pileup::kUsed};
+        }
+        zv[z] = pileup::ZmwView{in[z].consensus, in[z].consensus_len, rv[z].data(), in[z].n_reads};
+    }
+}
+
+// re of a read from its transcript's read columns (pbccs_pileup_columns, where the caller gives no re)
+int read_end(const pileup::ReadView& r)
+{
+    int nq = 0;
+    for (int k = 0; k < r.trLen; ++k) nq += r.tr[k] != 'D';
+    return r.rb + nq;
+}
+}  // namespace
+
+void pbccs_pileup_options_default(pbccs_pileup_options* o)
+{
+    if (!o) return;
+    o->band.mode = PBCCS_BAND_OFF;
+    o->band.w = 0;
+}
+
+int pbccs_pileup_columns(pbccs_engine* eng, const pbccs_pileup_columns_input* in, int n, pbccs_pileup_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    if (bad_columns_input(in, n)) return fail(PBCCS_EINVAL, "bad pbccs_pileup_columns_input");
+    return guarded([&] {
+        std::vector<std::vector<pileup::ReadView>> rv;
+        std::vector<pileup::ZmwView> zv;
+        columns_views(in, n, rv, zv);
+        std::vector<pileup::ZmwOut> zo((size_t)n);
+        for (int z = 0; z < n; ++z) zo[z] = pile_out_view(out[z]);
+        {
+            std::lock_guard<std::mutex> lk(eng->pileupMu);
+            eng->Pileup().Run(zv.data(), n, zo.data(), nullptr);   // vets every read before any device work
+        }
+        for (int z = 0; z < n; ++z) {
+            pile_outputs(zo[z], zv[z], out[z]);
+            for (int k = 0; k < zv[z].n; ++k) {
+                const bool used = !out[z].read_status || out[z].read_status[k] == PBCCS_KIN_USED;
+                if (out[z].re) out[z].re[k] = used ? read_end(rv[z][k]) : rv[z][k].rb;
+                if (out[z].transcript_lens) out[z].transcript_lens[k] = 0;
+            }
+        }
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_pileup_msa(pbccs_engine* eng, const pbccs_pileup_columns_input* in, int n, int* widths, int* const* cols,
+                     char* const* rows)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !widths))) return fail(PBCCS_EINVAL, "bad argument");
+    if (bad_columns_input(in, n)) return fail(PBCCS_EINVAL, "bad pbccs_pileup_columns_input");
+    return guarded([&] {
+        std::vector<std::vector<pileup::ReadView>> rv;
+        std::vector<pileup::ZmwView> zv;
+        columns_views(in, n, rv, zv);
+        std::vector<pileup::MsaOut> mo((size_t)n);
+        for (int z = 0; z < n; ++z)
+            mo[z] = pileup::MsaOut{0, cols ? cols[z] : nullptr, rows ? rows[z] : nullptr, widths[z]};
+        {
+            std::lock_guard<std::mutex> lk(eng->pileupMu);
+            eng->Pileup().Run(zv.data(), n, nullptr, mo.data());
+        }
+        for (int z = 0; z < n; ++z) widths[z] = mo[z].width;
+        return PBCCS_OK;
+    });
+}
+
+namespace {
+// One slice of pbccs_pileup_batch: ZMWs [z0, z1)
+void pileup_slice(pbccs_engine* eng, const pbccs_pileup_input* in, int z0, int z1, const pbccs_pileup_options& opts,
+                  pbccs_pileup_output* out)
+{
+    const int n = z1 - z0;
+    PlaceStage st;
+    place_and_align(eng, in, z0, z1, opts.band, st);
+    std::vector<pbccs_kinetics_output*> kout((size_t)n);
+    long long placed = 0, shared = 0;
+    for (int g = 0; g < n; ++g) {
+        kout[g] = in[z0 + g].kinetics;
+        placed += in[z0 + g].n_reads;
+        if (kout[g]) shared += in[z0 + g].n_reads;
+    }
+    kinetics_of_stage(eng, in, z0, st, kout);
+    std::vector<std::vector<pileup::ReadView>> rv((size_t)n);
+    std::vector<pileup::ZmwView> zv((size_t)n);
+    std::vector<pileup::ZmwOut> zo((size_t)n);
+    for (int g = 0; g < n; ++g) {
+        const pbccs_pileup_input& m = in[z0 + g];
+        rv[g].resize((size_t)m.n_reads);
+        for (int r = 0; r < m.n_reads; ++r) {
+            const PlacedRead& p = st.reads[g][r];
+            rv[g][r] = pileup::ReadView{p.tr, p.trLen, m.seqs[r], m.lens[r], p.rc, p.rb, p.tb, p.te, p.skip};
+        }
+        zv[g] = pileup::ZmwView{m.consensus, m.consensus_len, rv[g].data(), m.n_reads};
+        zo[g] = pile_out_view(out[z0 + g]);
+    }
+    {
+        std::lock_guard<std::mutex> lk(eng->pileupMu);
+        pileup::PileupRunner& run = eng->Pileup();
+        run.Run(zv.data(), n, zo.data(), nullptr);
+        run.stats.placed += placed;
+        run.stats.shared += shared;
+    }
+    for (int g = 0; g < n; ++g) {
+        pbccs_pileup_output& o = out[z0 + g];
+        pile_outputs(zo[g], zv[g], o);
+        for (int r = 0; r < zv[g].n; ++r) {
+            const PlacedRead& p = st.reads[g][r];
+            if (o.re) o.re[r] = p.re;
+            const bool used = p.skip == pileup::kUsed && p.tr;
+            if (o.transcript_lens) o.transcript_lens[r] = used ? p.trLen : 0;
+            if (used && o.transcripts && o.transcripts[r] && p.trLen > 0 &&
+                p.trLen <= in[z0 + g].consensus_len + in[z0 + g].lens[r])
+                std::memcpy(o.transcripts[r], p.tr, (size_t)p.trLen);
+        }
+    }
+}
+}  // namespace
+
+int pbccs_pileup_batch(pbccs_engine* eng, const pbccs_pileup_input* in, int n, const pbccs_pileup_options* opts,
+                       pbccs_pileup_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    pbccs_pileup_options o;
+    pbccs_pileup_options_default(&o);
+    if (opts) o = *opts;
+    if (o.band.mode != PBCCS_BAND_OFF && o.band.mode != PBCCS_BAND_AUTO && o.band.mode != PBCCS_BAND_WIDTH)
+        return fail(PBCCS_EINVAL, "unknown band mode");
+    if (o.band.mode == PBCCS_BAND_WIDTH && o.band.w < 0) return fail(PBCCS_EINVAL, "negative band half-width");
+    for (int g = 0; g < n; ++g) {
+        const pbccs_pileup_input& m = in[g];
+        if (!m.consensus || m.consensus_len <= 0) return fail(PBCCS_EINVAL, "empty consensus");
+        if (m.n_reads < 0 || (m.n_reads > 0 && (!m.seqs || !m.lens)))
+            return fail(PBCCS_EINVAL, "bad pbccs_pileup_input");
+        if (m.consensus_len > map::kMaxLen) return fail(PBCCS_EINVAL, "consensus longer than 65535");
+        for (int r = 0; r < m.n_reads; ++r) {
+            if (m.lens[r] < 0 || (m.lens[r] > 0 && !m.seqs[r]))
+                return fail(PBCCS_EINVAL, "bad read (NULL sequence or negative length)");
+            if (m.lens[r] > map::kMaxLen) return fail(PBCCS_EINVAL, "read longer than 65535");
+        }
+    }
+    return guarded([&] {
+        // slices as pbccs_kinetics_batch's
+        constexpr long long kSliceBases = 32LL << 20;
+        int z0 = 0;
+        while (z0 < n) {
+            long long bases = 0;
+            int z1 = z0;
+            while (z1 < n) {
+                long long b = 0;
+                for (int r = 0; r < in[z1].n_reads; ++r) b += in[z1].lens[r];
+                if (z1 > z0 && bases + b > kSliceBases) break;
+                bases += b;
+                ++z1;
+            }
+            pileup_slice(eng, in, z0, z1, o, out);
+            z0 = z1;
+        }
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_pileup_stats_get(pbccs_engine* eng, pbccs_pileup_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->pileupMu);
+        const pileup::PileStats s = eng->pileupRunner ? eng->pileupRunner->stats : pileup::PileStats();
+        *out = pbccs_pileup_stats{s.reads,    s.unmapped, s.emptyExtent, s.alignFailed, s.columns, s.slots, s.launches,
+                                  s.placed,   s.shared,   s.columnsMs,   s.reduceMs,    s.scanMs,  s.rowsMs};
+        if (reset && eng->pileupRunner) eng->pileupRunner->stats = pileup::PileStats();
         return PBCCS_OK;
     });
 }

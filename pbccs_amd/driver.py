@@ -185,7 +185,8 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
-              polish_window=None, rich_qvs=False, kinetics=False, strand_sites=False, directional=None):
+              polish_window=None, rich_qvs=False, kinetics=False, strand_sites=False, directional=None,
+              pileup=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -212,6 +213,13 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     strand_sites / directional (pbccs_ccs_batch_strand): as polish_zmws' keywords -- the results also
     carry strand_sites and, for the ZMWs polished once more per strand, the "fwd" and "rev" sub-records, their
     add_read_results / zscores indexed by input subread like the joint record's.  Not with polish_window (ValueError).
+    pileup (pbccs_pileup_batch, after the native call): True, or a dict with any of "msa", "transcripts", "arrays"
+    (booleans) and "band": every ZMW that ended Success or PoorQuality also carries "pileup", what pbccs_amd.pileup.pileup_batch
+    returns for its final consensus and the subreads whose add_read_results entry is SUCCESS (with
+    "msa" the gapped rows too, with "transcripts" each read's transcript, with "arrays" numpy arrays instead of nested
+    lists, which is much cheaper for large calls), and "ec", the effective coverage.  The
+    pileup's arrays run in the consensus's direction for both strands, unlike the kinetics arrays.  With kinetics
+    and pileup together the reads are placed and aligned once, in one native call for both.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -234,6 +242,11 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         for z, c in enumerate(chunks):
             if c["reads"] and not any(r.get("ip") is not None or r.get("pw") is not None for r in c["reads"]):
                 raise ValueError(f"ccs_batch(kinetics=True): the reads of chunk {z} carry no ip / pw tracks")
+    pile_opts = None
+    if pileup:   # before any engine is touched
+        pile_opts = {} if pileup is True else pileup
+        if not isinstance(pile_opts, dict) or set(pile_opts) - {"msa", "transcripts", "band", "arrays"}:
+            raise ValueError('ccs_batch(pileup=...): True, or a dict with any of "msa", "transcripts", "band", "arrays"')
     eng = engine or default_engine()
     settings = settings or ConsensusSettings()
     n = len(chunks)
@@ -381,14 +394,25 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         if sb is not None:
             res[-1]["strand_sites"] = sb.sites(z)
             res[-1].update(sb.sub_records(z))
-    if kinetics:
-        from .kinetics import kinetics_batch
+    if kinetics or pile_opts is not None:
         todo = [z for z in range(n) if res[z]["status_code"] in (0, 6) and res[z]["consensus"]]
-        got = kinetics_batch([(res[z]["consensus"],
-                               [{"seq": r["seq"], "ip": r.get("ip"), "pw": r.get("pw")}
-                                for r, a in zip(chunks[z]["reads"], res[z]["add_read_results"]) if a == 0])
-                              for z in todo], engine=eng)
-        for z, g in zip(todo, got):
-            g.pop("read_status")
-            res[z].update(g)
+        zin = [(res[z]["consensus"],
+                [{"seq": r["seq"], "ip": r.get("ip"), "pw": r.get("pw")}
+                 for r, a in zip(chunks[z]["reads"], res[z]["add_read_results"]) if a == 0])
+               for z in todo]
+        if pile_opts is None:
+            from .kinetics import kinetics_batch
+            got, piles = kinetics_batch(zin, engine=eng), None
+        else:   # one run of the placement and alignment stage for both
+            from .pileup import _batch
+            piles, got = _batch(zin, pile_opts.get("band"), bool(pile_opts.get("transcripts")),
+                                bool(pile_opts.get("msa")), eng, bool(kinetics), bool(pile_opts.get("arrays")))
+        if got is not None:
+            for z, g in zip(todo, got):
+                g.pop("read_status")
+                res[z].update(g)
+        if piles is not None:
+            for z, g in zip(todo, piles):
+                res[z]["pileup"] = g
+                res[z]["ec"] = g["ec"]
     return res

@@ -331,6 +331,51 @@ class CKineticsStats(ctypes.Structure):
                 ("columns_ms", ctypes.c_double), ("reduce_ms", ctypes.c_double)]
 
 
+class CPileupRead(ctypes.Structure):
+    _fields_ = [("transcript", ctypes.c_char_p), ("transcript_len", ctypes.c_int), ("rc", ctypes.c_int),
+                ("rb", ctypes.c_int), ("tb", ctypes.c_int), ("te", ctypes.c_int), ("seq", ctypes.c_char_p),
+                ("len", ctypes.c_int)]
+
+
+class CPileupColumnsInput(ctypes.Structure):
+    _fields_ = [("consensus", ctypes.c_char_p), ("consensus_len", ctypes.c_int), ("n_reads", ctypes.c_int),
+                ("reads", ctypes.POINTER(CPileupRead))]
+
+
+class CPileupOutput(ctypes.Structure):
+    _fields_ = [("counts", ctypes.POINTER(ctypes.c_int)), ("ins_reads", ctypes.POINTER(ctypes.c_int)),
+                ("ins_bases", ctypes.POINTER(ctypes.c_int)), ("slot_cov", ctypes.POINTER(ctypes.c_int)),
+                ("max_ins", ctypes.POINTER(ctypes.c_int)), ("cov", ctypes.POINTER(ctypes.c_int)),
+                ("plurality", ctypes.POINTER(ctypes.c_ubyte)), ("ins_plurality", ctypes.POINTER(ctypes.c_ubyte)),
+                ("read_status", ctypes.POINTER(ctypes.c_int)), ("n_match", ctypes.POINTER(ctypes.c_int)),
+                ("n_mismatch", ctypes.POINTER(ctypes.c_int)), ("n_ins", ctypes.POINTER(ctypes.c_int)),
+                ("n_del", ctypes.POINTER(ctypes.c_int)), ("rc", ctypes.POINTER(ctypes.c_int)),
+                ("rb", ctypes.POINTER(ctypes.c_int)), ("re", ctypes.POINTER(ctypes.c_int)),
+                ("tb", ctypes.POINTER(ctypes.c_int)), ("te", ctypes.POINTER(ctypes.c_int)),
+                ("transcripts", ctypes.POINTER(ctypes.c_char_p)), ("transcript_lens", ctypes.POINTER(ctypes.c_int)),
+                ("cov_sum", ctypes.c_longlong), ("n_used", ctypes.c_int * 2)]
+
+
+class CPileupInput(ctypes.Structure):
+    _fields_ = [("consensus", ctypes.c_char_p), ("consensus_len", ctypes.c_int), ("n_reads", ctypes.c_int),
+                ("seqs", ctypes.POINTER(ctypes.c_char_p)), ("lens", ctypes.POINTER(ctypes.c_int)),
+                ("ip", ctypes.POINTER(ctypes.POINTER(ctypes.c_ushort))),
+                ("pw", ctypes.POINTER(ctypes.POINTER(ctypes.c_ushort))),
+                ("kinetics", ctypes.POINTER(CKineticsOutput))]
+
+
+class CPileupOptions(ctypes.Structure):
+    _fields_ = [("band", CAlignBand)]
+
+
+class CPileupStats(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_longlong), ("skipped_unmapped", ctypes.c_longlong),
+                ("skipped_empty_extent", ctypes.c_longlong), ("skipped_align_failed", ctypes.c_longlong),
+                ("columns", ctypes.c_longlong), ("slots", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("placed", ctypes.c_longlong), ("shared", ctypes.c_longlong), ("columns_ms", ctypes.c_double),
+                ("reduce_ms", ctypes.c_double), ("scan_ms", ctypes.c_double), ("rows_ms", ctypes.c_double)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -508,6 +553,14 @@ SIGNATURES = {
     "pbccs_kinetics_batch": (I, [P, ctypes.POINTER(CKineticsInput), I, ctypes.POINTER(CKineticsOptions),
                                  ctypes.POINTER(CKineticsOutput)]),
     "pbccs_kinetics_stats_get": (I, [P, ctypes.POINTER(CKineticsStats), I]),
+    # subread pileup
+    "pbccs_pileup_options_default": (None, [ctypes.POINTER(CPileupOptions)]),
+    "pbccs_pileup_columns": (I, [P, ctypes.POINTER(CPileupColumnsInput), I, ctypes.POINTER(CPileupOutput)]),
+    "pbccs_pileup_batch": (I, [P, ctypes.POINTER(CPileupInput), I, ctypes.POINTER(CPileupOptions),
+                               ctypes.POINTER(CPileupOutput)]),
+    "pbccs_pileup_msa": (I, [P, ctypes.POINTER(CPileupColumnsInput), I, PI, ctypes.POINTER(PI),
+                             ctypes.POINTER(ctypes.c_char_p)]),
+    "pbccs_pileup_stats_get": (I, [P, ctypes.POINTER(CPileupStats), I]),
 }
 # bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
 DIGIT_SIGNATURES = {
