@@ -1339,6 +1339,82 @@ typedef struct {
 } pbccs_pileup_stats;
 int pbccs_pileup_stats_get(pbccs_engine* eng, pbccs_pileup_stats* out, int reset);
 
+/* ---- split mapping: a read fused across a missed adapter, placed on the draft as a chain of segments -----------
+ * The read as given is on the rows for both orientations; orientation 0 has the draft on the columns, orientation
+ * 1 its reverse complement (N <-> M as pbccs_map_batch's complement).  With pbccs_map_batch's scores and candidate
+ * order, every cell of row i has Start value G(i - 1), where G(0) = 0 and G(i) = max(G(i - 1), R(i).score -
+ * jump_penalty), R(i) being row i's best cell over both orientations (the larger score, then orientation 0, then
+ * the smaller column).  The chain ends at the first row with the largest R(i).score, which is the chain score; it
+ * is walked back through the cells' start cells into segments (DESIGN.md §3.25 has the full rule).  The DP runs on
+ * the device (k_split_fill, k_split_chain); one record per read row reaches device memory and only the segments
+ * return.  The reference has no such step. */
+#define PBCCS_SPLIT_JUMP_PENALTY 150   /* twice the measured null of unrelated sequence, DESIGN.md §3.25 */
+#define PBCCS_SPLIT_MAX_SEGMENTS 8     /* the default; at most 64 */
+
+typedef struct {
+    int* n_segments;   /* n_reads: the chain's segment count; 0: not mapped (no read, or a chain score of 0) */
+    int* truncated;    /* n_reads: 1 when the chain has more than max_segments segments */
+    int* score;        /* n_reads: the chain score = sum of the segments' own scores - jump_penalty * (count - 1) */
+    int* segments;     /* n_reads * max_segments * 6: per segment rc, extent on the read as given [begin, end),
+                          extent on the draft [begin, end), own score; the chain's last min(count, max_segments)
+                          segments in read order, the rest zero */
+} pbccs_split_map_output;
+
+/* jump_penalty < 0 is PBCCS_SPLIT_JUMP_PENALTY; max_segments <= 0 is PBCCS_SPLIT_MAX_SEGMENTS.  Any output array
+ * may be NULL.  PBCCS_EINVAL before any device work as pbccs_map_batch, and for max_segments above 64.  The row
+ * records (20 bytes per read row) and, for a draft wider than the widest register tile (512 columns), the per-read
+ * row buffer (16 bytes per column) live in a workspace; the batch is split into launches that fit
+ * PBCCS_SPLIT_WORKSPACE_KB (default 262144), and a read whose own buffers exceed it is left unmapped and makes the
+ * call return PBCCS_EOOM after every other read was mapped, with no device work for that read. */
+int pbccs_split_map_batch(pbccs_engine* eng, const pbccs_map_input* in, int n, int jump_penalty, int max_segments,
+                          pbccs_split_map_output* out);
+
+/* Split-mapping work since the last reset: reads given, DP cells (2 I J per read that reached the device), kernel
+ * launches, reads that ran on the row-buffer path, device ms (profiling on). */
+typedef struct {
+    long long jobs, cells, launches, tiled;
+    double device_ms;
+} pbccs_split_map_stats;
+int pbccs_split_map_stats_get(pbccs_engine* eng, pbccs_split_map_stats* out, int reset);
+
+/* pbccs_ccs_batch that recovers missed-adapter reads.  Once a ZMW's draft exists, every subread FilterReads dropped
+ * (at least twice the median full-pass length) whose placeholder the polish input would hold is split-mapped onto
+ * the draft (pbccs_split_map_batch's rule, one call per POA chunk).  It is accepted as a missed-adapter read when
+ * the chain is not truncated, has at least two segments, consecutive segments alternate orientation, and at least
+ * two segments reach min_length read bases.  Each such segment becomes a polish read -- the read's bases [begin,
+ * end) as given, in the read's own coordinates, on the segment's strand and draft extent -- and together they
+ * replace the one placeholder in place, so they reach AddRead last, in read order.  Interior segments are full
+ * passes; the first needs the read's ADAPTER_BEFORE, the last its ADAPTER_AFTER.  A read that is not accepted, or
+ * that the mapper cannot take (longer than 65535, or a draft that long), stays the placeholder it is. */
+typedef struct {
+    int jump_penalty;   /* < 0: PBCCS_SPLIT_JUMP_PENALTY */
+    int max_segments;   /* <= 0: PBCCS_SPLIT_MAX_SEGMENTS; at most 64 */
+} pbccs_split_options;
+void pbccs_split_options_default(pbccs_split_options* o);
+
+typedef struct {
+    int cap;                  /* in: segments the arrays below hold; add_order holds n_subreads + cap entries */
+    int n_reads;              /* out: subreads accepted as missed-adapter reads */
+    int n_segments;           /* out: their segments that became polish reads, in AddRead order */
+    int n_missed_adapters;    /* out: sum over the accepted reads of chain segments - 1 */
+    int n_added;              /* out: entries of add_order */
+    int* subread;             /* per segment: the caller's subread index */
+    int* segments;            /* per segment 6 ints: rc, read begin/end, draft begin/end, own score */
+    unsigned char* full_pass; /* per segment */
+    int* add_read_results;    /* per segment: as pbccs_zmw_output's */
+    double* zscores;          /* per segment */
+    int* add_order;           /* the ZMW's AddRead order in subread indices, a split subread once per added segment;
+                                 pbccs_ccs_output's add_order holds its first n_subreads entries */
+} pbccs_ccs_split_output;
+
+/* As pbccs_ccs_batch_ex4 without windows (extras may carry rich, not repeats), plus the split step.  The
+ * add_read_results / zscores of a split subread stay -1 / NaN in `out`; its segments' are in split_out.  PBCCS_ERANGE
+ * after everything else was written when a ZMW has more segments than cap.  split NULL is the defaults. */
+int pbccs_ccs_batch_split(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                          const pbccs_poa_options* poa, const pbccs_polish_options* opts,
+                          const pbccs_polish_extras* extras, const pbccs_split_options* split,
+                          pbccs_ccs_split_output* split_out, pbccs_ccs_output* out);
+
 #ifdef __cplusplus
 }
 #endif

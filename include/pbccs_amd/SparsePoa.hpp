@@ -9,7 +9,8 @@
 //   PacBio::CCS::SparsePoa                                 include/pacbio/ccs/SparsePoa.h:87-131
 //   ConsensusCore::PoaConsensus::FindConsensus             ConsensusCore/include/ConsensusCore/Poa/PoaConsensus.hpp:60-97
 //   PacBio::CCS::SparseAlign<K>, SdpRangeFinder::FindAnchors  SparseAlignment.hpp (included below)
-// Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch); a banded
+// Beyond the reference: PacBio::CCS::MapToDraft (reads placed on a finished draft, pbccs_map_batch) and
+// SplitMapToDraft (a fused read placed as a chain of segments, pbccs_split_map_batch); a banded
 // switch on SparsePoa (alignments filled inside SdpRangeFinder's ranges, which the reference computes and then
 // ignores), with AlignableRanges / TryAddRead to look at one alignment, and SdpRangeFinder::InitRangeFinder /
 // FindAlignableRange over a SparsePoa's graph (SparseAlignment.hpp).
@@ -234,6 +235,53 @@ inline std::vector<PoaAlignmentSummary> MapToDraft(const std::string& draft, con
         summaries[k].AlignmentScore = (float)score[k];
     }
     return summaries;
+}
+
+// SplitMapToDraft(draft, reads, jumpPenalty, maxSegments): each read placed on the draft as a chain of LOCAL
+// segments, on either strand, at jumpPenalty per extra segment -- what a read that holds several passes fused
+// across a missed adapter needs (pbccs_split_map_batch, one call, no graph; the reference has no such step).  Each
+// segment is a PoaAlignmentSummary whose ExtentOnRead is in the coordinates of the read as given (also when
+// ReverseComplementedRead) and whose AlignmentScore is the segment's own score.
+struct SplitAlignment {
+    std::vector<PoaAlignmentSummary> Segments;   // the chain's last maxSegments segments, in read order
+    int NumSegments = 0;                         // the chain's segment count; 0: the read was not mapped
+    bool Truncated = false;
+    int Score = 0;                               // sum of the segments' own scores - jumpPenalty * (NumSegments - 1)
+};
+
+inline std::vector<SplitAlignment> SplitMapToDraft(const std::string& draft, const std::vector<std::string>& reads,
+                                                   int jumpPenalty = PBCCS_SPLIT_JUMP_PENALTY,
+                                                   int maxSegments = PBCCS_SPLIT_MAX_SEGMENTS)
+{
+    const int n = (int)reads.size();
+    if (maxSegments < 1 || maxSegments > 64) throw std::invalid_argument("SplitMapToDraft: 1 <= maxSegments <= 64");
+    std::vector<const char*> p;
+    std::vector<int> len;
+    for (const std::string& r : reads) {
+        p.push_back(r.data());
+        len.push_back((int)r.size());
+    }
+    std::vector<int> count(n + 1), trunc(n + 1), score(n + 1), segs(6 * (size_t)maxSegments * (n + 1));
+    const pbccs_map_input in{draft.data(), (int)draft.size(), p.data(), len.data(), n};
+    pbccs_split_map_output out{count.data(), trunc.data(), score.data(), segs.data()};
+    ConsensusCore::detail::Check(pbccs_split_map_batch(ConsensusCore::detail::DefaultEngine(), &in, 1, jumpPenalty,
+                                                       maxSegments, &out));
+    std::vector<SplitAlignment> res(n);
+    for (int k = 0; k < n; ++k) {
+        res[k].NumSegments = count[k];
+        res[k].Truncated = trunc[k] != 0;
+        res[k].Score = score[k];
+        for (int g = 0; g < count[k] && g < maxSegments; ++g) {
+            const int* v = &segs[6 * ((size_t)k * maxSegments + g)];
+            PoaAlignmentSummary sm;
+            sm.ReverseComplementedRead = v[0] != 0;
+            sm.ExtentOnRead = Interval(v[1], v[2]);
+            sm.ExtentOnConsensus = Interval(v[3], v[4]);
+            sm.AlignmentScore = (float)v[5];
+            res[k].Segments.push_back(sm);
+        }
+    }
+    return res;
 }
 
 }  // namespace CCS

@@ -29,6 +29,7 @@
 #include "kinetics_kernels.hpp"
 #include "pileup_kernels.hpp"
 #include "map_kernels.hpp"
+#include "split_map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
 #include "sparse_kernels.hpp"
@@ -112,6 +113,14 @@ struct pbccs_engine {
         if (!mapper) mapper.reset(new map::MapRunner(device));
         mapper->profiling = profiling;
         return *mapper;
+    }
+    // the split mapper's workspace (made on first use), on the mapper's stream and under mapMu as well
+    std::unique_ptr<map::SplitMapRunner> splitMapper;
+    map::SplitMapRunner& SplitMap()
+    {
+        if (!splitMapper) splitMapper.reset(new map::SplitMapRunner(device, Map().stream()));
+        splitMapper->profiling = profiling;
+        return *splitMapper;
     }
     // SparseAlign's workspace (made on first use): its own stream; calls on one engine take turns on it
     std::unique_ptr<sparse::SparseRunner> sparseRunner;
@@ -3064,6 +3073,69 @@ int pbccs_map_stats_get(pbccs_engine* eng, pbccs_map_stats* out, int reset)
     });
 }
 
+// ---- split mapping (split_map_kernels.hpp) ------------------------------------------------------------------
+int pbccs_split_map_batch(pbccs_engine* eng, const pbccs_map_input* in, int n, int jump_penalty, int max_segments,
+                          pbccs_split_map_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!in || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    if (jump_penalty < 0) jump_penalty = PBCCS_SPLIT_JUMP_PENALTY;
+    if (max_segments <= 0) max_segments = PBCCS_SPLIT_MAX_SEGMENTS;
+    if (max_segments > map::kSplitMaxSegments) return fail(PBCCS_EINVAL, "max_segments above 64");
+    for (int g = 0; g < n; ++g) {
+        const pbccs_map_input& m = in[g];
+        if (!m.draft || m.draft_len <= 0) return fail(PBCCS_EINVAL, "empty draft");
+        if (m.n_reads < 0 || (m.n_reads > 0 && (!m.seqs || !m.lens))) return fail(PBCCS_EINVAL, "bad pbccs_map_input");
+        if (m.draft_len > map::kMaxLen) return fail(PBCCS_EINVAL, "draft longer than 65535");
+        for (int r = 0; r < m.n_reads; ++r) {
+            if (m.lens[r] < 0 || (m.lens[r] > 0 && !m.seqs[r]))
+                return fail(PBCCS_EINVAL, "bad read (NULL sequence or negative length)");
+            if (m.lens[r] > map::kMaxLen) return fail(PBCCS_EINVAL, "read longer than 65535");
+        }
+    }
+    return guarded([&] {
+        std::vector<map::MapGroup> groups(n);
+        for (int g = 0; g < n; ++g)
+            groups[g] = map::MapGroup{in[g].draft, in[g].draft_len, in[g].seqs, in[g].lens, in[g].n_reads};
+        std::vector<map::SplitMapResult> res;
+        {
+            std::lock_guard<std::mutex> lk(eng->mapMu);
+            eng->SplitMap().Run(groups.data(), n, jump_penalty, max_segments, &res);
+        }
+        bool oom = false;
+        size_t k = 0;
+        for (int g = 0; g < n; ++g)
+            for (int r = 0; r < in[g].n_reads; ++r, ++k) {
+                const map::SplitMapResult& m = res[k];
+                oom = oom || m.status == PBCCS_EOOM;
+                if (out[g].n_segments) out[g].n_segments[r] = m.count;
+                if (out[g].truncated) out[g].truncated[r] = m.truncated;
+                if (out[g].score) out[g].score[r] = m.score;
+                if (out[g].segments) {
+                    int* sg = out[g].segments + (size_t)r * max_segments * 6;
+                    std::fill(sg, sg + (size_t)max_segments * 6, 0);
+                    for (const map::SplitSeg& s : m.segs) {
+                        const int v[6] = {s.rc, s.rb, s.re, s.tb, s.te, s.score};
+                        sg = std::copy(v, v + 6, sg);
+                    }
+                }
+            }
+        if (oom) return fail(PBCCS_EOOM, "a read's buffers exceed the split-map workspace (PBCCS_SPLIT_WORKSPACE_KB)");
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_split_map_stats_get(pbccs_engine* eng, pbccs_split_map_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->mapMu);
+        const map::SplitMapStats s = eng->splitMapper ? eng->splitMapper->stats : map::SplitMapStats();
+        *out = pbccs_split_map_stats{s.jobs, s.cells, s.launches, s.tiled, s.deviceMs};
+        if (reset && eng->splitMapper) eng->splitMapper->stats = map::SplitMapStats();
+        return PBCCS_OK;
+    });
+}
+
 // ---- consensus kinetics (kinetics_kernels.hpp) -------------------------------------------------------------
 namespace {
 // ConsensusCore Sequence.cpp:44-105 (ComplementArray; note N <-> M), as k_map_fill's complement()
@@ -4240,7 +4312,45 @@ struct CcsChunk {
     std::vector<std::vector<int>> arr;
     std::vector<std::vector<double>> zsc;
     bool draftRange = false;   // a draft longer than its caller buffer
+    // per polish position: the caller's subread (-1: a placeholder of a read FilterReads dropped) and, for a
+    // segment of a split read (pbccs_ccs_batch_split), its index in segs
+    std::vector<std::vector<int>> posSub, posSeg;
+    struct SplitSegment {
+        int subread;
+        map::SplitSeg seg;
+        unsigned char full;
+    };
+    std::vector<std::vector<SplitSegment>> segs;
+    std::vector<int> nSplit, nMissed;
 };
+
+// A read FilterReads dropped and its split mapping: accepted as a missed-adapter read when the chain is whole, has at
+// least two segments on alternating strands, and at least two of them reach minLength read bases.  Those segments
+// become polish reads cut from the read as given (its own coordinates: no Appendix A.15 quirk); interior segments
+// are full passes, the first needs the read's ADAPTER_BEFORE, the last its ADAPTER_AFTER.
+static bool split_read(const driver::Subread& read, int subread, const map::SplitMapResult& chain, size_t minLength,
+                       std::vector<driver::MappedRead>* reads, std::vector<CcsChunk::SplitSegment>* segs)
+{
+    reads->clear();
+    segs->clear();
+    if (chain.truncated || chain.segs.size() < 2) return false;
+    for (size_t k = 1; k < chain.segs.size(); ++k)
+        if (chain.segs[k].rc == chain.segs[k - 1].rc) return false;
+    for (size_t k = 0; k < chain.segs.size(); ++k) {
+        const map::SplitSeg& sg = chain.segs[k];
+        if ((size_t)(sg.re - sg.rb) < minLength) continue;
+        driver::MappedRead mr;
+        mr.seq = read.seq.substr(sg.rb, sg.re - sg.rb);
+        mr.strand = sg.rc ? 1 : 0;
+        mr.ts = sg.tb;
+        mr.te = sg.te;
+        reads->push_back(std::move(mr));
+        const bool full = (k > 0 || (read.flags & driver::kAdapterBefore)) &&
+                          (k + 1 < chain.segs.size() || (read.flags & driver::kAdapterAfter));
+        segs->push_back(CcsChunk::SplitSegment{subread, sg, (unsigned char)(full ? 1 : 0)});
+    }
+    return reads->size() >= 2;
+}
 
 // The chunk's polish outputs: the caller's pbccs_zmw_output fields, but per-read arrays owned by the chunk.
 static void bind_polish_outputs(CcsChunk* C, const pbccs_ccs_output* out)
@@ -4259,7 +4369,8 @@ static void bind_polish_outputs(CcsChunk* C, const pbccs_ccs_output* out)
 static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const pbccs_polish_options& o,
                             long long max_poa_coverage, bool mapPastCap, bool bandedPoa,
                             const std::vector<std::vector<driver::Subread>>& sub,
-                            const std::vector<std::vector<int>>& order, pbccs_ccs_output* out, CcsChunk* C)
+                            const std::vector<std::vector<int>>& order, pbccs_ccs_output* out, CcsChunk* C,
+                            const pbccs_split_options* split = nullptr)
 {
     const size_t m = C->zs.size();
     std::vector<std::vector<const std::string*>> poaReads(m);
@@ -4306,7 +4417,57 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
     };
     poa::PoaBatch(eng->PoaRunners(), poaReads, max_poa_coverage, -1, &C->css, &keys, &rc, &ext,
                   mapPastCap ? &mapSlice : nullptr, bandedPoa);
+    // split: the reads FilterReads dropped, ZMW by ZMW in input order, split-mapped onto the finished drafts in one
+    // call; splitRes[q] holds one chain per dropped read of ZMW q (empty: nothing to place, or no draft to place on)
+    std::vector<std::vector<int>> droppedOf(m);
+    std::vector<std::vector<map::SplitMapResult>> splitRes(m);
+    if (split) {
+        std::vector<map::MapGroup> groups;
+        std::vector<size_t> groupQ;
+        std::vector<std::vector<const char*>> ptrs(m);
+        std::vector<std::vector<int>> lens(m);
+        for (size_t q = 0; q < m; ++q) {
+            const int z = C->zs[q];
+            const std::string& css = C->css[q];
+            if ((int)css.size() < o.min_length || css.empty() || (int)css.size() > map::kMaxLen) continue;
+            bool slot = false;   // a placeholder the polish input will hold
+            for (size_t i = 0; i < keys[q].size() && (keys[q][i] != -2 || mapPastCap); ++i)
+                slot = slot || order[z][i] < 0;
+            if (!slot) continue;
+            std::vector<char> kept(sub[z].size(), 0);
+            for (int k : order[z])
+                if (k >= 0) kept[k] = 1;
+            for (size_t k = 0; k < sub[z].size(); ++k) {
+                if (kept[k]) continue;
+                const bool fits = !sub[z][k].seq.empty() && (int)sub[z][k].seq.size() <= map::kMaxLen;
+                droppedOf[q].push_back((int)k);
+                ptrs[q].push_back(fits ? sub[z][k].seq.data() : nullptr);   // too long for the mapper: stays dropped
+                lens[q].push_back(fits ? (int)sub[z][k].seq.size() : 0);
+            }
+            groups.push_back(map::MapGroup{css.data(), (int)css.size(), ptrs[q].data(), lens[q].data(), (int)ptrs[q].size()});
+            groupQ.push_back(q);
+        }
+        if (!groups.empty()) {
+            std::vector<map::SplitMapResult> res;
+            {
+                std::lock_guard<std::mutex> lk(eng->mapMu);
+                eng->SplitMap().Run(groups.data(), (int)groups.size(), split->jump_penalty, split->max_segments, &res);
+            }
+            size_t at = 0;
+            for (size_t g = 0; g < groups.size(); ++g) {
+                splitRes[groupQ[g]].assign(res.begin() + at, res.begin() + at + groups[g].n);
+                at += (size_t)groups[g].n;
+            }
+            for (const map::SplitMapResult& r : res)
+                if (r.status != PBCCS_OK) throw DeviceOom("a read's buffers exceed the split-map workspace");
+        }
+    }
     C->mapped.resize(m);
+    C->posSub.resize(m);
+    C->posSeg.resize(m);
+    C->segs.resize(m);
+    C->nSplit.assign(m, 0);
+    C->nMissed.assign(m, 0);
     C->seqPtr.resize(m);
     C->lens.resize(m);
     C->strands.resize(m);
@@ -4327,11 +4488,34 @@ static void ccs_draft_chunk(pbccs_engine* eng, const pbccs_ccs_input* in, const 
         }
         std::vector<unsigned char> added;
         const std::vector<int>& kk = keys[q];
-        size_t past = 0;
+        size_t past = 0, nextDropped = 0;
+        std::vector<driver::MappedRead> segReads;
+        std::vector<CcsChunk::SplitSegment> segRecs;
         for (size_t i = 0; i < kk.size() && (kk[i] != -2 || mapPastCap); ++i) {
             driver::MappedRead mr;
             const int key = kk[i];
             bool ok;
+            if (order[z][i] < 0 && nextDropped < splitRes[q].size()) {
+                // the k-th placeholder stands for the k-th dropped read: replaced in place by its segments
+                const size_t d = nextDropped++;
+                const int k = droppedOf[q][d];
+                if (split_read(sub[z][k], k, splitRes[q][d], (size_t)o.min_length, &segReads, &segRecs)) {
+                    for (size_t g = 0; g < segReads.size(); ++g) {
+                        C->mapped[q].push_back(segReads[g]);
+                        added.push_back(1);
+                        C->full[q].push_back(segRecs[g].full);
+                        C->posSub[q].push_back(k);
+                        C->posSeg[q].push_back((int)C->segs[q].size());
+                        C->segs[q].push_back(segRecs[g]);
+                    }
+                    C->nSplit[q]++;
+                    C->nMissed[q] += splitRes[q][d].count - 1;
+                    if (key == -2) ++past;   // its mapRes entry (a read never mapped) is passed over
+                    continue;
+                }
+            }
+            C->posSub[q].push_back(order[z][i]);
+            C->posSeg[q].push_back(-1);
             if (key == -2) {
                 const map::MapResult& r = mapRes[q][past++];
                 ok = r.mapped && driver::ExtractMappedRead(sub[z][order[z][i]], r.rc != 0, r.ext[0], r.ext[1], r.ext[2],
@@ -4378,9 +4562,16 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                           bool mapPastCap, bool bandedPoa, const pbccs_polish_options* opts, pbccs_ccs_output* out,
                           const pbccs_window_options* win = nullptr, pbccs_window_info* info = nullptr,
                           pbccs_rich_qvs* rich = nullptr, const pbccs_strand_options* strand = nullptr,
-                          pbccs_strand_result* sres = nullptr)
+                          pbccs_strand_result* sres = nullptr, const pbccs_split_options* split = nullptr,
+                          pbccs_ccs_split_output* splitOut = nullptr)
 {
     if (!eng || n < 0 || (n > 0 && (!in || !out)) || max_poa_coverage < 1) return fail(PBCCS_EINVAL, "bad argument");
+    if (split && (win || strand || (n > 0 && !splitOut)))
+        return fail(PBCCS_EINVAL, "split reads take no windows and no strand screen, and need their outputs");
+    for (int z = 0; split && z < n; ++z) {
+        splitOut[z].n_reads = splitOut[z].n_segments = splitOut[z].n_missed_adapters = splitOut[z].n_added = 0;
+        if (splitOut[z].cap < 0) return fail(PBCCS_EINVAL, "bad pbccs_ccs_split_output");
+    }
     if (strand && (win || !sres || !strand_options_ok(*strand)))
         return fail(PBCCS_EINVAL, "the strand screen takes no windows, needs its outputs and valid options");
     for (int z = 0; rich && z < n; ++z) rich[z].len = 0;   // ZMWs that never reach the polish
@@ -4560,7 +4751,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             }
             const double d0 = since();
             try {
-                ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, bandedPoa, sub, order, out, &chunks[c]);
+                ccs_draft_chunk(eng, in, o, max_poa_coverage, mapPastCap, bandedPoa, sub, order, out, &chunks[c], split);
                 if (rich)
                     for (int z : chunks[c].pinZ) chunks[c].prich.push_back(rich[z]);
                 if (strand) {
@@ -4641,7 +4832,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                                        nullptr, rich ? C.prich.data() : nullptr, strand ? &sc : nullptr);
             if (r != PBCCS_OK) return r;
         }
-        bool draftRange = false;
+        bool draftRange = false, splitRange = false;
         for (const CcsChunk& C : chunks) {
             draftRange = draftRange || C.draftRange;
             for (size_t q = 0; q < C.pinZ.size(); ++q) {
@@ -4656,13 +4847,38 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
                 // polish position i is FilterReads' i-th read, i.e. caller subread order[z][i]; the scorer's reads
                 // (AddRead calls) are the positions with a result, in position order
                 int added = 0;
-                for (size_t i = 0; i < C.mapped[q].size(); ++i) {
-                    const int k = order[z][i];
-                    if (k < 0) continue;
-                    if (arrOut) arrOut[k] = C.arr[q][i];
-                    if (zsOut) zsOut[k] = C.zsc[q][i];
-                    if (out[z].add_order && C.arr[q][i] >= 0) out[z].add_order[added++] = k;
+                pbccs_ccs_split_output* so = split ? &splitOut[z] : nullptr;
+                if (so) {
+                    so->n_reads = C.nSplit[q];
+                    so->n_missed_adapters = C.nMissed[q];
+                    so->n_segments = (int)C.segs[q].size();
+                    if (so->n_segments > so->cap) splitRange = true;
                 }
+                for (size_t i = 0; i < C.mapped[q].size(); ++i) {
+                    const int k = C.posSub[q][i];
+                    if (k < 0) continue;
+                    const int g = C.posSeg[q][i];
+                    if (g >= 0) {   // a segment of a split read: the subread's own entries stay -1 / NaN
+                        if (g >= so->cap) continue;
+                        const CcsChunk::SplitSegment& sg = C.segs[q][g];
+                        const int v[6] = {sg.seg.rc, sg.seg.rb, sg.seg.re, sg.seg.tb, sg.seg.te, sg.seg.score};
+                        if (so->subread) so->subread[g] = sg.subread;
+                        if (so->segments) std::copy(v, v + 6, so->segments + 6 * (size_t)g);
+                        if (so->full_pass) so->full_pass[g] = sg.full;
+                        if (so->add_read_results) so->add_read_results[g] = C.arr[q][i];
+                        if (so->zscores) so->zscores[g] = C.zsc[q][i];
+                    } else {
+                        if (arrOut) arrOut[k] = C.arr[q][i];
+                        if (zsOut) zsOut[k] = C.zsc[q][i];
+                    }
+                    if (C.arr[q][i] < 0) continue;
+                    // with split reads there can be more AddRead calls than subreads: the whole order goes to the
+                    // split output, the caller's add_order holds as much of it as it has room for
+                    if (so && so->add_order && added < in[z].n_subreads + so->cap) so->add_order[added] = k;
+                    if (out[z].add_order && added < in[z].n_subreads) out[z].add_order[added] = k;
+                    ++added;
+                }
+                if (so) so->n_added = added;
             }
         }
         // the strand screen's second half over the polish inputs of every chunk: sites, split
@@ -4727,6 +4943,7 @@ static int ccs_batch_impl(pbccs_engine* eng, const pbccs_ccs_input* in, int n, l
             }
         }
         if (draftRange) return fail(PBCCS_ERANGE, "draft buffer too small");
+        if (splitRange) return fail(PBCCS_ERANGE, "split segment buffers too small");
         return strandRc == PBCCS_ERANGE ? fail(PBCCS_ERANGE, "strand site buffers too small") : PBCCS_OK;
     });
 }
@@ -4800,6 +5017,33 @@ int pbccs_ccs_batch_strand(pbccs_engine* eng, const pbccs_ccs_input* in, int n, 
     if (strand) so = *strand;
     return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out,
                           nullptr, nullptr, extras ? extras->rich : nullptr, &so, strand_out);
+}
+
+void pbccs_split_options_default(pbccs_split_options* o)
+{
+    if (!o) return;
+    o->jump_penalty = PBCCS_SPLIT_JUMP_PENALTY;
+    o->max_segments = PBCCS_SPLIT_MAX_SEGMENTS;
+}
+
+int pbccs_ccs_batch_split(pbccs_engine* eng, const pbccs_ccs_input* in, int n, const pbccs_ccs_options* ccs,
+                          const pbccs_poa_options* poa, const pbccs_polish_options* opts,
+                          const pbccs_polish_extras* extras, const pbccs_split_options* split,
+                          pbccs_ccs_split_output* split_out, pbccs_ccs_output* out)
+{
+    if (n > 0 && !split_out) return fail(PBCCS_EINVAL, "bad argument");
+    if (extras && extras->repeats) return fail(PBCCS_EINVAL, "the ccs calls take no repeat options");
+    pbccs_ccs_options c;
+    if (ccs) c = *ccs;
+    else pbccs_ccs_options_default(&c);
+    pbccs_split_options so;
+    pbccs_split_options_default(&so);
+    if (split) so = *split;
+    if (so.jump_penalty < 0) so.jump_penalty = PBCCS_SPLIT_JUMP_PENALTY;
+    if (so.max_segments <= 0) so.max_segments = PBCCS_SPLIT_MAX_SEGMENTS;
+    if (so.max_segments > map::kSplitMaxSegments) return fail(PBCCS_EINVAL, "max_segments above 64");
+    return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out,
+                          nullptr, nullptr, extras ? extras->rich : nullptr, nullptr, nullptr, &so, split_out);
 }
 
 }  // extern "C"

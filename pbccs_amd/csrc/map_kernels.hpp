@@ -80,6 +80,9 @@ public:
     // whose own buffers exceed it gets status PBCCS_EOOM and no device work.
     void Run(const MapGroup* groups, int ng, float minScoreToAdd, std::vector<MapResult>* out);
 
+    // the engine's mapping stream (SplitMapRunner queues its work on it too)
+    hipStream_t stream() const { return stream_; }
+
     MapStats stats;
     bool profiling = false;
 

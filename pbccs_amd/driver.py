@@ -120,7 +120,69 @@ def _past_cap(rest, summaries, min_length):
     return out
 
 
-def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None):
+def dropped_reads(reads, min_length):
+    """(index, read) of the reads filter_reads sets to None (at least twice the median full-pass length), in input
+    order: the k-th None of filter_reads' order stands for the k-th of them."""
+    order = filter_reads(reads, min_length)
+    kept = {id(r) for r in order if r is not None}
+    return [(k, r) for k, r in enumerate(reads) if id(r) not in kept] if order else []
+
+
+def split_options(split_long_reads):
+    """(jump_penalty or None, max_segments) of the split_long_reads keyword: True, or a dict with any of
+    "jump_penalty" and "max_segments"."""
+    opts = {} if split_long_reads is True else split_long_reads
+    if not isinstance(opts, dict) or set(opts) - {"jump_penalty", "max_segments"}:
+        raise ValueError('split_long_reads: False, True, or a dict with any of "jump_penalty", "max_segments"')
+    return opts.get("jump_penalty"), int(opts.get("max_segments", 8))
+
+
+def split_read(read, chain, min_length):
+    """A read FilterReads dropped and its split mapping (mapping.split_map_to_draft's entry) -> the polish reads of
+    a missed-adapter read, or None when it is not accepted as one.  Accepted: not truncated, at least two segments,
+    consecutive segments on alternating strands, at least two segments of min_length read bases.  Each such segment
+    becomes {"seq", "strand", "ts", "te", "full_pass", "segment"} in read order, its sequence cut from the read as
+    given in the read's own coordinates (no Appendix A.15 quirk).  Interior segments are full passes; the first
+    needs the read's ADAPTER_BEFORE, the last its ADAPTER_AFTER."""
+    if chain is None or chain["truncated"] or len(chain["segments"]) < 2:
+        return None
+    segs = chain["segments"]
+    if any(a["rc"] == b["rc"] for a, b in zip(segs, segs[1:])):
+        return None
+    flags = read.get("flags", FULL_PASS)
+    out = []
+    for k, sg in enumerate(segs):
+        b, e = sg["read"]
+        if e - b < min_length:
+            continue
+        full = (k > 0 or bool(flags & ADAPTER_BEFORE)) and (k + 1 < len(segs) or bool(flags & ADAPTER_AFTER))
+        out.append({"seq": read["seq"][b:e], "strand": 1 if sg["rc"] else 0, "ts": int(sg["tpl"][0]),
+                    "te": int(sg["tpl"][1]), "full_pass": full, "segment": dict(sg)})
+    return out if len(out) >= 2 else None
+
+
+def _apply_splits(zmw, slots, dropped, chains, min_length):
+    """Replaces, in place, the placeholder of every accepted missed-adapter read by its segments' polish reads.
+    slots: positions in zmw["reads"] of the dropped reads' placeholders, in order; dropped: dropped_reads();
+    chains: one split mapping per dropped read.  Records the accepted reads in zmw["split_reads"] ("segments": the
+    ones that became reads, "n_segments": the chain's count)."""
+    reads, split = [], []
+    at = {pos: k for k, pos in enumerate(slots)}
+    for pos, r in enumerate(zmw["reads"]):
+        k = at.get(pos)
+        got = split_read(dropped[k][1], chains[k], min_length) if k is not None and k < len(dropped) else None
+        if got is None:
+            reads.append(r)
+            continue
+        split.append({"subread": dropped[k][0], "first": len(reads), "n_segments": chains[k]["n_segments"],
+                      "segments": [g.pop("segment") for g in got]})
+        reads += got
+    zmw["reads"] = reads
+    zmw["split_reads"] = split
+    zmw["n_missed_adapters"] = sum(s["n_segments"] - 1 for s in split)
+
+
+def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None, split_mapper=None):
     """One ZMW's subreads -> the polish boundary's ZMW dict, or (status, None) when the ZMW ends before the
     scorer: NoSubreads (Consensus.h:414-420) or TooShort (:427-434).
 
@@ -128,7 +190,11 @@ def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None):
     {"draft", "snr", "reads"} and reads holds one entry per POA key in order: the mapped read, or a
     placeholder {"seq": None} for a read the POA or ExtractMappedRead skipped.
     mapper (optional, a callable with mapping.map_to_draft's contract): the reads past max_poa_coverage are
-    placed on the draft with it and follow the POA's reads, one entry per read of FilterReads' order."""
+    placed on the draft with it and follow the POA's reads, one entry per read of FilterReads' order.
+    split_mapper (optional, a callable (draft, reads) with mapping.split_map_to_draft's results): every read
+    FilterReads dropped is split-mapped onto the draft, and one accepted as a missed-adapter read (split_read) has
+    its placeholder replaced in place by its segments' reads; zmw then also holds "split_reads" ([{"subread",
+    "first", "segments"}], first being the position of its first read) and "n_missed_adapters"."""
     reads = filter_reads(chunk["reads"], min_length)
     if not reads or all(r is None for r in reads):
         return "NoSubreads", None
@@ -143,15 +209,23 @@ def zmw_input(chunk, poa, min_length=10, max_poa_coverage=None, mapper=None):
         rest = reads[len(keys):]
         summ = iter(mapper(draft, [r["seq"] for r in rest if r is not None]) if any(r is not None for r in rest) else [])
         out += _past_cap(rest, [None if r is None else next(summ) for r in rest], min_length)
-    return None, {"draft": draft, "snr": list(chunk["snr"]), "reads": out}
+    zmw = {"draft": draft, "snr": list(chunk["snr"]), "reads": out}
+    if split_mapper is not None:
+        dropped = dropped_reads(chunk["reads"], min_length)
+        slots = [i for i, r in enumerate(reads[:len(out)]) if r is None]
+        _apply_splits(zmw, slots, dropped, split_mapper(draft, [r["seq"] for _, r in dropped]) if slots else [],
+                      min_length)
+    return None, zmw
 
 
 def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, map_past_cap=False,
-                     banded_poa=False):
+                     banded_poa=False, split_long_reads=False):
     """zmw_input for many ZMWs at once, with the POA of all of them on the GPU in one pbccs_poa_batch
     (every ZMW adds its next subread in the same device round).  Returns [(status, zmw)] as zmw_input.
     map_past_cap: the reads past max_poa_coverage of all ZMWs are placed on their drafts in one pbccs_map_batch.
-    banded_poa: the POA fills inside SdpRangeFinder's ranges (poa.poa_batch(banded=True))."""
+    banded_poa: the POA fills inside SdpRangeFinder's ranges (poa.poa_batch(banded=True)).
+    split_long_reads (False, True, or {"jump_penalty", "max_segments"}): the reads FilterReads dropped of all ZMWs
+    are split-mapped onto their drafts in one pbccs_split_map_batch, as zmw_input's split_mapper."""
     from . import poa as _poa
     filtered = [filter_reads(c["reads"], min_length) for c in chunks]
     idx = [z for z, rs in enumerate(filtered) if rs and not all(r is None for r in rs)]
@@ -181,12 +255,29 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
             mr = extract_mapped_read(filtered[z][i], r["summaries"][key], min_length) if key >= 0 else None
             reads.append(mr if mr is not None else {"seq": None, "strand": 0, "ts": 0, "te": 0, "full_pass": False})
         out[z] = (None, {"draft": draft, "snr": list(chunks[z]["snr"]), "reads": reads})
+    if split_long_reads:
+        from . import mapping as _mapping
+        jump, max_seg = split_options(split_long_reads)
+        todo = []
+        for z in idx:
+            if out[z][1] is None:
+                continue
+            slots = [i for i, r in enumerate(filtered[z][:len(out[z][1]["reads"])]) if r is None]
+            dropped = dropped_reads(chunks[z]["reads"], min_length)
+            # a read or draft the mapper cannot take (map::kMaxLen) stays the placeholder it is
+            ok = len(out[z][1]["draft"]) <= 65535
+            todo.append((z, slots, dropped, [r["seq"] if ok and len(r["seq"]) <= 65535 else None for _, r in dropped]
+                         if slots else []))
+        got = _mapping.split_map_batch([(out[z][1]["draft"], seqs) for z, _, _, seqs in todo], jump, max_seg,
+                                       engine=engine)
+        for (z, slots, dropped, _), chains in zip(todo, got):
+            _apply_splits(out[z][1], slots, dropped, chains, min_length)
     return out
 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
               polish_window=None, rich_qvs=False, kinetics=False, strand_sites=False, directional=None,
-              pileup=False):
+              pileup=False, split_long_reads=False):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -220,6 +311,14 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     lists, which is much cheaper for large calls), and "ec", the effective coverage.  The
     pileup's arrays run in the consensus's direction for both strands, unlike the kinetics arrays.  With kinetics
     and pileup together the reads are placed and aligned once, in one native call for both.
+    split_long_reads (pbccs_ccs_batch_split): False, True, or a dict with any of "jump_penalty" and
+    "max_segments".  Every subread FilterReads dropped for its length is split-mapped onto the draft; one that is a
+    chain of at least two segments on alternating strands (not truncated, two of them at least min_length long) is
+    taken for a read fused across a missed adapter, and its segments reach AddRead in its place, last, in read order.
+    The results then also carry "split_reads": [{"subread", "segments": [{"rc", "read", "tpl", "score", "full_pass",
+    "add_read_result", "zscore"}]}] and "n_missed_adapters" (the sum of the chains' segments - 1); the subread's
+    own add_read_results / zscores entries stay -1 / NaN (so kinetics and pileup leave it out), and "add_order"
+    repeats its index once per added segment.  Not with polish_window, strand_sites or directional (ValueError).
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -231,6 +330,11 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     from .polish import ConsensusSettings
     from .quiver import _struct_dtype
     strand = None
+    split = None
+    if split_long_reads:
+        if polish_window is not None or strand_sites or directional is not None:
+            raise ValueError("split_long_reads does not run with polish_window, strand_sites or directional")
+        split = split_options(split_long_reads)
     if directional is None and settings is not None:
         directional = getattr(settings, "directional", None)
     if strand_sites or directional is not None:
@@ -313,7 +417,37 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
             rich["cap"][:n] = caps
         x = L.CPolishExtras()
         x.rich = ctypes.cast(rich.ctypes.data, ctypes.POINTER(L.CRichQvs))
-    if strand is not None:
+    if split is not None:
+        x = x if rich_qvs else L.CPolishExtras()
+        jump, max_seg = split
+        if not 1 <= max_seg <= 64 or (jump is not None and jump < 0):
+            raise ValueError("split_long_reads: jump_penalty >= 0 and 1 <= max_segments <= 64")
+        so = L.CSplitOptions(-1 if jump is None else int(jump), max_seg)
+        scap = counts * max_seg                        # segments per ZMW: every subread split max_seg ways
+        sfirst = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(scap, out=sfirst[1:])
+        stot = max(1, int(sfirst[-1]))
+        s_sub, s_seg = np.zeros(stot, dtype=np.int32), np.zeros(6 * stot, dtype=np.int32)
+        s_full, s_arr = np.zeros(stot, dtype=np.uint8), np.zeros(stot, dtype=np.int32)
+        s_zs, s_order = np.zeros(stot, dtype=np.float64), np.zeros(stot + max(1, nr_all), dtype=np.int32)
+        souts = np.zeros(max(1, n), dtype=_struct_dtype(L.CCcsSplitOutput))
+        if n:
+            s0 = sfirst[:-1]
+            souts["cap"][:n] = scap
+            souts["subread"][:n] = s_sub.ctypes.data + 4 * s0
+            souts["segments"][:n] = s_seg.ctypes.data + 24 * s0
+            souts["full_pass"][:n] = s_full.ctypes.data + s0
+            souts["add_read_results"][:n] = s_arr.ctypes.data + 4 * s0
+            souts["zscores"][:n] = s_zs.ctypes.data + 8 * s0
+            souts["add_order"][:n] = s_order.ctypes.data + 4 * (s0 + f0)
+        co = L.CCcsOptions(mc, 1 if map_past_cap else 0)
+        po = L.CPoaOptions(mc, -1, 1 if banded_poa else 0)
+        L.check(L.load().pbccs_ccs_batch_split(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                               ctypes.byref(co), ctypes.byref(po), ctypes.byref(opts), ctypes.byref(x),
+                                               ctypes.byref(so),
+                                               ctypes.cast(souts.ctypes.data, ctypes.POINTER(L.CCcsSplitOutput)),
+                                               ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    elif strand is not None:
         from .strand import SiteBuffers
         x = x if rich_qvs else L.CPolishExtras()
         sb = SiteBuffers(caps.tolist(), counts.tolist())
@@ -394,6 +528,18 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         if sb is not None:
             res[-1]["strand_sites"] = sb.sites(z)
             res[-1].update(sb.sub_records(z))
+        if split is not None:
+            s0, ns = int(sfirst[z]), int(souts["n_segments"][z])
+            by_sub = {}
+            for g in range(s0, s0 + ns):
+                sg = s_seg[6 * g:6 * g + 6].tolist()
+                by_sub.setdefault(int(s_sub[g]), []).append(
+                    {"rc": bool(sg[0]), "read": (sg[1], sg[2]), "tpl": (sg[3], sg[4]), "score": sg[5],
+                     "full_pass": bool(s_full[g]), "add_read_result": int(s_arr[g]), "zscore": float(s_zs[g])})
+            res[-1]["split_reads"] = [{"subread": k, "segments": v} for k, v in by_sub.items()]
+            res[-1]["n_missed_adapters"] = int(souts["n_missed_adapters"][z])
+            a0 = s0 + f
+            res[-1]["add_order"] = s_order[a0:a0 + int(souts["n_added"][z])].tolist()
     if kinetics or pile_opts is not None:
         todo = [z for z in range(n) if res[z]["status_code"] in (0, 6) and res[z]["consensus"]]
         zin = [(res[z]["consensus"],

@@ -214,6 +214,28 @@ class CMapStats(ctypes.Structure):
                 ("strips", ctypes.c_longlong), ("device_ms", ctypes.c_double)]
 
 
+class CSplitMapOutput(ctypes.Structure):
+    _fields_ = [("n_segments", ctypes.POINTER(ctypes.c_int)), ("truncated", ctypes.POINTER(ctypes.c_int)),
+                ("score", ctypes.POINTER(ctypes.c_int)), ("segments", ctypes.POINTER(ctypes.c_int))]
+
+
+class CSplitMapStats(ctypes.Structure):
+    _fields_ = [("jobs", ctypes.c_longlong), ("cells", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("tiled", ctypes.c_longlong), ("device_ms", ctypes.c_double)]
+
+
+class CSplitOptions(ctypes.Structure):
+    _fields_ = [("jump_penalty", ctypes.c_int), ("max_segments", ctypes.c_int)]
+
+
+class CCcsSplitOutput(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_int), ("n_reads", ctypes.c_int), ("n_segments", ctypes.c_int),
+                ("n_missed_adapters", ctypes.c_int), ("n_added", ctypes.c_int),
+                ("subread", ctypes.POINTER(ctypes.c_int)), ("segments", ctypes.POINTER(ctypes.c_int)),
+                ("full_pass", ctypes.POINTER(ctypes.c_ubyte)), ("add_read_results", ctypes.POINTER(ctypes.c_int)),
+                ("zscores", ctypes.POINTER(ctypes.c_double)), ("add_order", ctypes.POINTER(ctypes.c_int))]
+
+
 class CCcsOptions(ctypes.Structure):
     _fields_ = [("max_poa_coverage", ctypes.c_longlong), ("map_past_cap", ctypes.c_int)]
 
@@ -503,6 +525,8 @@ SIGNATURES = {
     # MapToDraft and the capped ccs that keeps every pass
     "pbccs_map_batch": (I, [P, ctypes.POINTER(CMapInput), I, ctypes.c_float, ctypes.POINTER(CMapOutput)]),
     "pbccs_map_stats_get": (I, [P, ctypes.POINTER(CMapStats), I]),
+    "pbccs_split_map_batch": (I, [P, ctypes.POINTER(CMapInput), I, I, I, ctypes.POINTER(CSplitMapOutput)]),
+    "pbccs_split_map_stats_get": (I, [P, ctypes.POINTER(CSplitMapStats), I]),
     "pbccs_ccs_options_default": (None, [ctypes.POINTER(CCcsOptions)]),
     "pbccs_ccs_batch_ex": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
                                ctypes.POINTER(CPolishOptions), ctypes.POINTER(CCcsOutput)]),
@@ -543,6 +567,11 @@ SIGNATURES = {
                                    ctypes.POINTER(CPoaOptions), ctypes.POINTER(CPolishOptions),
                                    ctypes.POINTER(CPolishExtras), ctypes.POINTER(CStrandOptions),
                                    ctypes.POINTER(CStrandResult), ctypes.POINTER(CCcsOutput)]),
+    "pbccs_split_options_default": (None, [ctypes.POINTER(CSplitOptions)]),
+    "pbccs_ccs_batch_split": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.POINTER(CCcsOptions),
+                                  ctypes.POINTER(CPoaOptions), ctypes.POINTER(CPolishOptions),
+                                  ctypes.POINTER(CPolishExtras), ctypes.POINTER(CSplitOptions),
+                                  ctypes.POINTER(CCcsSplitOutput), ctypes.POINTER(CCcsOutput)]),
     "pbccs_scorer_strand_scores": (I, [P, PM, I, PD, PD, PI, PI]),
     "pbccs_scorer_strand_sites": (I, [P, ctypes.POINTER(CStrandOptions), PI, PI, ctypes.POINTER(ctypes.c_char), PD,
                                       PD, I, PI]),

@@ -85,3 +85,88 @@ def map_stats(engine=None, reset=False):
     s = _L.CMapStats()
     _L.check(load().pbccs_map_stats_get(eng._h, ctypes.byref(s), 1 if reset else 0))
     return {k: getattr(s, k) for k, _ in _L.CMapStats._fields_}
+
+
+SPLIT_JUMP_PENALTY = 150   # PBCCS_SPLIT_JUMP_PENALTY: twice the measured null of unrelated sequence
+
+
+def split_map_batch(zmws, jump_penalty=None, max_segments=8, engine=None):
+    """Split mapping (pbccs_split_map_batch): every read is placed on its draft as a chain of LOCAL
+    segments, on either strand, at jump_penalty per extra segment -- what a read that holds several passes fused
+    across a missed adapter needs.  zmws: [(draft, [read or None, ...])].  Returns per ZMW a list with one entry per
+    read: None for a read that was not mapped (no read, or a chain score of 0), else {"score", "n_segments",
+    "truncated", "segments": [{"rc", "read": (b, e), "tpl": (b, e), "score"}]} -- the chain's last max_segments
+    segments in read order, extents on the read as given and on the draft, each with its own score; "score" is
+    their sum less jump_penalty per jump.  jump_penalty None is SPLIT_JUMP_PENALTY.
+
+    Marshalling is flat, as map_batch's."""
+    import numpy as np
+    from .quiver import _struct_dtype
+    eng = _engine(engine)
+    P = SPLIT_JUMP_PENALTY if jump_penalty is None else int(jump_penalty)
+    ms = int(max_segments)
+    if P < 0 or not 1 <= ms <= 64:
+        raise ValueError("split_map_batch: jump_penalty >= 0 and 1 <= max_segments <= 64")
+    n = len(zmws)
+    counts = np.fromiter((len(reads) for _, reads in zmws), dtype=np.int64, count=n)
+    drafts = [d.encode() for d, _ in zmws]
+    enc = [b"" if r is None else r.encode() for _, reads in zmws for r in reads]
+    nr = len(enc)
+    lens = np.fromiter((len(e) for e in enc), dtype=np.int32, count=nr)
+    dlens = np.fromiter((len(d) for d in drafts), dtype=np.int64, count=n)
+    blob = ctypes.create_string_buffer(b"".join(enc) + b"".join(drafts), max(1, int(lens.sum()) + int(dlens.sum())))
+    starts = np.zeros(nr + 1, dtype=np.int64)
+    np.cumsum(lens, out=starts[1:])
+    ptrs = (ctypes.addressof(blob) + starts[:-1]).astype(np.uint64)
+    ptrs[lens == 0] = 0                                   # NULL: no read
+    dstarts = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(dlens, out=dstarts[1:])
+    first = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=first[1:])
+    nseg = np.zeros(max(1, nr), dtype=np.int32)
+    trunc = np.zeros(max(1, nr), dtype=np.int32)
+    score = np.zeros(max(1, nr), dtype=np.int32)
+    segs = np.zeros(max(1, nr) * ms * 6, dtype=np.int32)
+    ins = np.zeros(max(1, n), dtype=_struct_dtype(_L.CMapInput))
+    outs = np.zeros(max(1, n), dtype=_struct_dtype(_L.CSplitMapOutput))
+    if n:
+        f0 = first[:-1]
+        ins["draft"][:n] = ctypes.addressof(blob) + int(starts[-1]) + dstarts[:-1]
+        ins["draft_len"][:n] = dlens
+        ins["seqs"][:n] = ptrs.ctypes.data + 8 * f0
+        ins["lens"][:n] = lens.ctypes.data + 4 * f0
+        ins["n_reads"][:n] = counts
+        outs["n_segments"][:n] = nseg.ctypes.data + 4 * f0
+        outs["truncated"][:n] = trunc.ctypes.data + 4 * f0
+        outs["score"][:n] = score.ctypes.data + 4 * f0
+        outs["segments"][:n] = segs.ctypes.data + 24 * ms * f0
+    _L.check(load().pbccs_split_map_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CMapInput)), n, P, ms,
+                                          ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CSplitMapOutput))))
+    n_l, t_l, sc_l, sg_l = nseg.tolist(), trunc.tolist(), score.tolist(), segs.tolist()
+    firsts, cnts = first.tolist(), counts.tolist()
+    res = []
+    for z in range(n):
+        row = []
+        for k in range(firsts[z], firsts[z] + cnts[z]):
+            if n_l[k] == 0:
+                row.append(None)
+                continue
+            at = 6 * ms * k
+            row.append({"score": sc_l[k], "n_segments": n_l[k], "truncated": bool(t_l[k]),
+                        "segments": [{"rc": bool(sg_l[a]), "read": (sg_l[a + 1], sg_l[a + 2]),
+                                      "tpl": (sg_l[a + 3], sg_l[a + 4]), "score": sg_l[a + 5]}
+                                     for a in range(at, at + 6 * min(n_l[k], ms), 6)]})
+        res.append(row)
+    return res
+
+
+def split_map_to_draft(draft, reads, jump_penalty=None, max_segments=8, engine=None):
+    """One entry per read, None when it was not mapped, else split_map_batch's chain."""
+    return split_map_batch([(draft, list(reads))], jump_penalty, max_segments, engine)[0]
+
+
+def split_map_stats(engine=None, reset=False):
+    eng = _engine(engine)
+    s = _L.CSplitMapStats()
+    _L.check(load().pbccs_split_map_stats_get(eng._h, ctypes.byref(s), 1 if reset else 0))
+    return {k: getattr(s, k) for k, _ in _L.CSplitMapStats._fields_}

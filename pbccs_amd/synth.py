@@ -50,6 +50,31 @@ def make_zmw(rng, length, passes, snr=(10.0, 7.0, 5.0, 11.0), read_errors=(0.07,
     return {"truth": truth.tobytes().decode(), "draft": draft.tobytes().decode(), "snr": list(snr), "reads": reads}
 
 
+ADAPTER = "ATCTCTCTCAACAACAACAACGGAGGAGGAGGAAAAGAGAGAGAT"   # the 45-base SMRTbell adapter a missed call leaves in
+
+
+def make_fused_read(rng, truth, passes, read_errors=(0.07, 0.04, 0.01), first_strand=0, adapter=ADAPTER):
+    """A subread a missed adapter left uncut: `passes` noisy passes of truth (a str) on alternating strands,
+    fused head to tail with a noisy adapter between them.  Returns {"seq", "passes": [(begin, end, strand)]} with
+    each pass's extent in the fused read."""
+    t = np.frombuffer(truth.encode(), dtype=np.uint8)
+    ad = np.frombuffer(adapter.encode(), dtype=np.uint8)
+    parts, where, at = [], [], 0
+    for k in range(passes):
+        if k:
+            a = _mutate(rng, ad, *read_errors)
+            parts.append(a)
+            at += a.shape[0]
+        r = _mutate(rng, t, *read_errors)
+        strand = (first_strand + k) % 2
+        if strand == 1:
+            r = COMP[r[::-1]]
+        parts.append(r)
+        where.append((at, at + int(r.shape[0]), strand))
+        at += int(r.shape[0])
+    return {"seq": np.concatenate(parts).tobytes().decode(), "passes": where}
+
+
 def make_zmws(n, length, passes, seed, snr=(10.0, 7.0, 5.0, 11.0), length_range=None, passes_range=None,
               random_snr=False):
     """n ZMWs.  length_range/passes_range (inclusive) draw per-ZMW sizes (config #4)."""
