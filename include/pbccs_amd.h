@@ -658,7 +658,9 @@ int pbccs_poa_stats_get(pbccs_engine* eng, pbccs_poa_stats* out, int reset);
  * bit-exact: scores, ties and the traceback come out as the reference's.  The DP runs on the device
  * (k_align_fill, one move byte per cell and no score matrix in memory; k_align_trace).  AlignLinear is not
  * provided; long near-identical pairs have the certified band below (pbccs_align_batch_ex), which
- * keeps these answers in memory linear in the band's width. */
+ * keeps these answers in memory linear in the band's width.  These calls are GLOBAL, as the reference's Align;
+ * the ends-free modes (SEMIGLOBAL, LOCAL) of the int32 aligner live in pbccs_align_batch_ends further down
+ * (k_align_fill_ends / k_align_trace_ends). */
 #define PBCCS_ALIGN_NW 0
 #define PBCCS_ALIGN_AFFINE 1
 #define PBCCS_ALIGN_AFFINE_IUPAC 2
@@ -769,6 +771,40 @@ typedef struct {
     double store_bytes, fill_ms, trace_ms;
 } pbccs_align_band_stats;
 int pbccs_align_band_stats_get(pbccs_engine* eng, pbccs_align_band_stats* out, int reset);
+
+/* ---- Ends-free pairwise alignment: SEMIGLOBAL and LOCAL ------------------------------
+ * The reference's Align stops at GLOBAL; these are the rules of its POA (PoaGraphImpl.cpp:178-352) on a graph that
+ * holds the target as one unbranched path, with the int32 AlignParams.  Query on rows i, target on columns j.
+ * S(0, j) = 0 (Start).  Column 0: SEMIGLOBAL S(i, 0) = i * Insert (Extra), LOCAL 0 (Start).  A cell tries, a later
+ * candidate winning only when strictly greater: (LOCAL) Start 0, the diagonal (Match / Mismatch by raw byte
+ * equality), Delete S(i, j-1) + Delete, Extra S(i-1, j) + Insert -- the POA's order, not Align's ArgMax3.  End cell:
+ * SEMIGLOBAL the smallest j holding the maximum of row I; LOCAL the maximum over all cells, ties to the smallest
+ * j, then the smallest i.  The walk goes back to the first Start cell; the transcript (M R for a diagonal step, D
+ * Delete, I Extra) covers target[target_begin, target_end) and query[query_begin, query_end), and the score is the
+ * end cell's.  SEMIGLOBAL always covers the whole query. */
+typedef struct {
+    int mode;           /* PBCCS_POA_SEMIGLOBAL or PBCCS_POA_LOCAL */
+    int both_strands;   /* != 0: the query is also aligned reverse complemented (ComplementArray, as pbccs_map_batch);
+                           forward wins iff its score >= the other's */
+} pbccs_align_ends;
+
+typedef struct {
+    int target_begin, target_end;
+    int query_begin, query_end;   /* in the coordinates of the sequence that was aligned (the reverse complement
+                                     when rc), as pbccs_map_batch's read extent */
+    int rc;
+} pbccs_align_extent;
+
+/* params->kind must be PBCCS_ALIGN_NW (the reference defines free ends for linear scores only; an affine kind is
+ * PBCCS_EINVAL); params->mode is ignored in favour of ends->mode.  PBCCS_EINVAL before any device work as well: a
+ * mode other than SEMIGLOBAL or LOCAL (GLOBAL is pbccs_align_batch's), Insert > 0 or Delete > 0 (a rewarding gap
+ * next to a free end has no reading), a bad pair.  out[k].score_i is the score; out[k].transcript the transcript of
+ * the two substrings ext[k] names.  An empty query gives score 0, an empty transcript and a zero extent; an empty
+ * target gives all I with score I * Insert (SEMIGLOBAL) or the same empty answer (LOCAL); neither launches.  The
+ * per-pair status, the int32 range rule, the workspace budget with its PBCCS_EOOM and the PBCCS_ERANGE contract
+ * are pbccs_align_batch's, and the work adds to pbccs_align_stats. */
+int pbccs_align_batch_ends(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_ends* ends,
+                           const pbccs_align_pair* pairs, int n, pbccs_align_result* out, pbccs_align_extent* ext);
 
 /* ---- MapToDraft: placing reads on a finished draft ---------------------------------------------------
  * What SparsePoa::OrientAndAddRead(read, minScoreToAdd) followed by FindConsensus reports for a read on a graph

@@ -16,6 +16,9 @@
 // BandOptions::Width(w) turns on the certified banded fill: a long, near-identical pair is filled
 // inside a band of diagonals, and the banded answer is returned only where its score proves it to be the full
 // fill's; every other pair takes the full fill.  The results are the same either way.
+//
+// Also not in the reference: AlignEnds, the SEMIGLOBAL and LOCAL modes of the int32 aligner.
+// Align itself goes on refusing them, as the reference does.
 #pragma once
 
 #include <algorithm>
@@ -257,6 +260,59 @@ inline PairwiseAlignment* AlignAffineIupac(const std::string& target, const std:
 {
     return detail::RunAlign(detail::AffineParams(PBCCS_ALIGN_AFFINE_IUPAC, params), {{target, query}}, band)
         .alignments[0];
+}
+
+// Not in the reference, whose Align stops at GLOBAL: the ends-free modes (pbccs_align_batch_ends).
+// What an alignment covers: target[TargetBegin, TargetEnd) and query[QueryBegin, QueryEnd), the query's in the
+// coordinates of the sequence that was aligned (the reverse complement when ReverseComplemented).
+struct AlignExtent {
+    int TargetBegin, TargetEnd, QueryBegin, QueryEnd;
+    bool ReverseComplemented;
+};
+
+// Sequence.cpp's ReverseComplement (ComplementArray; note N <-> M): the sequence bothStrands aligns
+inline std::string ReverseComplementOf(const std::string& s)
+{
+    static const char from[] = "ACGTacgtNMnm-", to[] = "TGCAtgcaMNmn-";
+    std::string r(s.rbegin(), s.rend());
+    for (char& c : r) {
+        char out = 127;
+        for (int k = 0; from[k]; ++k)
+            if (c == from[k]) out = to[k];
+        if (c >= 0 && c <= 3) out = (char)(3 - c);
+        c = out;
+    }
+    return r;
+}
+
+// SEMIGLOBAL (the whole query inside the target) or LOCAL alignment by the POA's rules on the target as one
+// unbranched path, with the int32 AlignParams.  Returns the alignment of the two substrings *extent names (caller
+// deletes); *score is the end cell's.  bothStrands also aligns the reverse complement of the query and keeps the
+// forward answer iff its score >= the other's.  Thrown before the engine is touched: GLOBAL (that is Align's) or
+// an unknown mode, Insert > 0 or Delete > 0 (InvalidInputError).
+inline PairwiseAlignment* AlignEnds(const std::string& target, const std::string& query, AlignMode mode,
+                                    AlignParams params, AlignExtent* extent, int* score = NULL,
+                                    bool bothStrands = false)
+{
+    if (mode != SEMIGLOBAL && mode != LOCAL)
+        throw InvalidInputError("AlignEnds takes SEMIGLOBAL or LOCAL; GLOBAL alignment is Align's");
+    if (params.Insert > 0 || params.Delete > 0)
+        throw InvalidInputError("SEMIGLOBAL and LOCAL alignment need Insert <= 0 and Delete <= 0");
+    const pbccs_align_params p = detail::NwParams(AlignConfig(params, mode));
+    const pbccs_align_ends e{(int)mode, bothStrands ? 1 : 0};
+    const pbccs_align_pair in{target.data(), (int)target.size(), query.data(), (int)query.size()};
+    std::string buf(target.size() + query.size() + 1, '\0');
+    pbccs_align_result out{&buf[0], (int)buf.size() - 1, 0, 0, 0.f, 0};
+    pbccs_align_extent x{0, 0, 0, 0, 0};
+    detail::Check(pbccs_align_batch_ends(detail::DefaultEngine(), &p, &e, &in, 1, &out, &x));
+    const std::string aligned = x.rc ? ReverseComplementOf(query) : query;
+    PairwiseAlignment* a = PairwiseAlignment::FromTranscript(
+        buf.substr(0, out.len), target.substr(x.target_begin, x.target_end - x.target_begin),
+        aligned.substr(x.query_begin, x.query_end - x.query_begin));
+    if (!a) throw DeviceError("the device returned a transcript that does not map the target onto the query");
+    if (extent) *extent = AlignExtent{x.target_begin, x.target_end, x.query_begin, x.query_end, x.rc != 0};
+    if (score) *score = out.score_i;
+    return a;
 }
 
 // The vector forms: every (target, query) pair in one device call, results in input order; caller deletes.

@@ -379,6 +379,7 @@ from .richqv import ConsensusRichQVs, rich_feature_tracks  # noqa: E402,F401
 from .align import (AffineAlignmentParams, Align, AlignAffine, AlignAffineIupac, AlignConfig,  # noqa: E402,F401
                     AlignParams, DefaultAffineAlignmentParams, IupacAwareAffineAlignmentParams, PairwiseAlignment,
                     TargetToQueryPositions, UnsupportedFeatureError, align_band_stats, align_batch, align_stats)
+from .align import AlignLocal, AlignSemiglobal, align_ends_batch  # noqa: E402,F401
 from .mapping import (map_batch, map_stats, map_to_draft, split_map_batch, split_map_stats,  # noqa: E402,F401
                       split_map_to_draft)
 from .sparse import SparseAlign, sparse_align_batch, sparse_align_stats  # noqa: E402,F401

@@ -359,6 +359,121 @@ def AlignAffineIupac(target, query, params=None, engine=None, band=None):
     return align_batch([(target, query)], AFFINE_IUPAC, params, engine, band=band)[0][0]
 
 
+def _c_ends(mode, params, both_strands, kind, band):
+    """The refusals of the ends-free modes, all on the host (before any engine is touched), and the C structs."""
+    if kind != NW or isinstance(params, AffineAlignmentParams):
+        raise UnsupportedFeatureError("SEMIGLOBAL and LOCAL alignment are defined for the linear (NW) scores only")
+    if not (band is None or band is False):
+        raise UnsupportedFeatureError("the certified band is GLOBAL only: it cannot be combined with a mode")
+    if mode == GLOBAL:
+        raise InvalidInputError("GLOBAL alignment is Align's / align_batch's")
+    if mode not in (SEMIGLOBAL, LOCAL):
+        raise InvalidInputError(f"unknown alignment mode {mode!r}")
+    if isinstance(params, AlignConfig):
+        params = params.Params
+    if params is None:
+        params = AlignParams.Default()
+    if params.Insert > 0 or params.Delete > 0:
+        raise InvalidInputError("SEMIGLOBAL and LOCAL alignment need Insert <= 0 and Delete <= 0")
+    c = _L.CAlignParams()
+    c.kind, c.mode = NW, mode
+    c.match, c.mismatch, c.insert, c.delete_ = params.Match, params.Mismatch, params.Insert, params.Delete
+    e = _L.CAlignEnds()
+    e.mode, e.both_strands = mode, 1 if both_strands else 0
+    return c, e
+
+
+def align_ends_batch(pairs, mode, params=None, both_strands=False, engine=None, kind=NW, band=None):
+    """Ends-free alignment of many (target, query) pairs in one call: mode SEMIGLOBAL (the whole
+    query inside the target: the target's ends are free) or LOCAL (the best pair of substrings).  The rules are the
+    reference POA's on a graph that holds the target as one unbranched path, with the int32 AlignParams (params;
+    default edit distance): candidates (LOCAL: Start,) diagonal, Delete, Extra, a later one only when strictly
+    greater; end cell the smallest target column, then the smallest query row, holding the maximum.
+
+    Returns ([PairwiseAlignment of the two substrings], [score], [extent]); an extent is {"target": (b, e),
+    "query": (b, e), "rc"}.  both_strands also aligns the reverse complement of the query and keeps the forward
+    answer iff its score >= the other's; "query" is then in the coordinates of the sequence that was aligned, as
+    map_batch's "read".  Refused: Insert > 0 or Delete > 0 and mode GLOBAL (InvalidInputError); an affine kind or
+    band= (UnsupportedFeatureError)."""
+    import numpy as np
+    from .quiver import _struct_dtype
+    c, e = _c_ends(mode, params, both_strands, kind, band)
+    if engine is None:
+        from . import default_engine
+        engine = default_engine()
+    n = len(pairs)
+    enc = [_encode(s) for p in pairs for s in p]
+    lens = np.fromiter((len(x) for x in enc), dtype=np.int64, count=2 * n)
+    blob = ctypes.create_string_buffer(b"".join(enc), max(1, int(lens.sum())))
+    starts = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(lens, out=starts[1:])
+    ptrs = (ctypes.addressof(blob) + starts[:-1]).astype(np.uint64)
+    cap = lens[0::2] + lens[1::2]
+    ostart = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(cap, out=ostart[1:])
+    obuf = ctypes.create_string_buffer(max(1, int(ostart[-1])))
+    ins = np.zeros(max(1, n), dtype=_struct_dtype(_L.CAlignPair))
+    outs = np.zeros(max(1, n), dtype=_struct_dtype(_L.CAlignResult))
+    exts = np.zeros(max(1, n), dtype=_struct_dtype(_L.CAlignExtent))
+    if n:
+        ins["target"][:n] = ptrs[0::2]
+        ins["target_len"][:n] = lens[0::2]
+        ins["query"][:n] = ptrs[1::2]
+        ins["query_len"][:n] = lens[1::2]
+        outs["transcript"][:n] = ctypes.addressof(obuf) + ostart[:-1]
+        outs["cap"][:n] = cap
+    _L.check(load().pbccs_align_batch_ends(engine._h, ctypes.byref(c), ctypes.byref(e),
+                                           ctypes.cast(ins.ctypes.data, ctypes.POINTER(_L.CAlignPair)), n,
+                                           ctypes.cast(outs.ctypes.data, ctypes.POINTER(_L.CAlignResult)),
+                                           ctypes.cast(exts.ctypes.data, ctypes.POINTER(_L.CAlignExtent))))
+    raw = obuf.raw
+    os_, ln, score = ostart.tolist(), outs["len"][:n].tolist(), outs["score_i"][:n].tolist()
+    tb, te = exts["target_begin"][:n].tolist(), exts["target_end"][:n].tolist()
+    qb, qe, rc = exts["query_begin"][:n].tolist(), exts["query_end"][:n].tolist(), exts["rc"][:n].tolist()
+    alns, extents = [], []
+    for k, (t, q) in enumerate(pairs):
+        tr = raw[os_[k]:os_[k] + ln[k]].decode("latin-1")
+        if rc[k]:
+            q = reverse_complement(q)
+        a = _from_device_transcript(tr, t[tb[k]:te[k]], q[qb[k]:qe[k]])
+        if a is None:
+            raise _L.PbccsError(-3, "the device returned a transcript that does not map the target onto the query")
+        alns.append(a)
+        extents.append({"target": (tb[k], te[k]), "query": (qb[k], qe[k]), "rc": bool(rc[k])})
+    return alns, score, extents
+
+
+def _complement_table():
+    t = bytearray([127]) * 256   # ComplementArray's value for every byte it does not name
+    for a, b in zip(b"ACGTacgtNMnm-\x00\x01\x02\x03", b"TGCAtgcaMNmn-\x03\x02\x01\x00"):
+        t[a] = b
+    return bytes(t)
+
+
+_COMPLEMENT = _complement_table()
+
+
+def reverse_complement(seq):
+    """ConsensusCore::ReverseComplement (Sequence.cpp's ComplementArray; note N <-> M): the sequence both_strands
+    aligns, and the one an rc extent's "query" indexes."""
+    out = _encode(seq)[::-1].translate(_COMPLEMENT)
+    return out if isinstance(seq, bytes) else out.decode("latin-1")
+
+
+def AlignSemiglobal(target, query, params=None, both_strands=False, engine=None, kind=NW, band=None):
+    """The whole query placed inside the target (the target's ends are free): (alignment of target[b:e] and the
+    query, score, extent).  See align_ends_batch."""
+    a, s, x = align_ends_batch([(target, query)], SEMIGLOBAL, params, both_strands, engine, kind, band)
+    return a[0], s[0], x[0]
+
+
+def AlignLocal(target, query, params=None, both_strands=False, engine=None, kind=NW, band=None):
+    """The best local match of the two sequences: (alignment of the two substrings, score, extent).  See
+    align_ends_batch."""
+    a, s, x = align_ends_batch([(target, query)], LOCAL, params, both_strands, engine, kind, band)
+    return a[0], s[0], x[0]
+
+
 def align_stats(engine=None, reset=False):
     if engine is None:
         from . import default_engine

@@ -9,7 +9,9 @@
 // decision, taken from the very values the fill computed), stored by (strip, step, lane, row-in-lane) so that a
 // step's store is one contiguous 64 R-byte write.  k_align_trace walks the bytes, one thread per pair.
 // DESIGN.md §3.14.  RunBanded is the opt-in certified band for long near-identical pairs (align_band.hpp,
-// align_band_kernels.hip); Run and RunKeep do not use it.
+// align_band_kernels.hip); Run and RunKeep do not use it.  RunEnds is the ends-free int32 aligner
+// (SEMIGLOBAL, LOCAL: k_align_fill_ends / k_align_trace_ends in align_modes_kernels.hip) on the
+// same workspace; Run, RunKeep and RunBanded stay GLOBAL.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,6 +29,8 @@ constexpr int kNw = 0, kAffine = 1, kAffineIupac = 2;   // PBCCS_ALIGN_*
 constexpr int kRowsPerLane[3] = {2, 4, 8};              // the compiled R values: strips of 128, 256, 512 rows
 constexpr int kTraceFlagged = 1;                        // trace status: the walk in M reached row 0 or column 0
 constexpr int kTraceLeftBand = 2;                       // banded trace status: the walk would read outside the band
+constexpr int kEndsSemiglobal = 1, kEndsLocal = 2;      // RunEnds' modes (PBCCS_POA_SEMIGLOBAL / _LOCAL)
+constexpr int kMoveDiag = 0, kMoveDelete = 1, kMoveExtra = 2, kMoveStart = 3;   // k_align_fill_ends' move bytes
 
 struct AlignScoring {
     int kind;
@@ -105,6 +109,12 @@ struct PairResult {
     int status = 0;   // PBCCS_OK / PBCCS_EINVAL / PBCCS_EOOM
 };
 
+// What an ends-free alignment covers: target[targetBegin, targetEnd) and query[queryBegin, queryEnd), the query's
+// in the coordinates of the sequence that was aligned (its reverse complement when rc).
+struct EndsExtent {
+    int targetBegin = 0, targetEnd = 0, queryBegin = 0, queryEnd = 0, rc = 0;
+};
+
 // One pair whose transcript stays on the device (RunKeep): what the host may know of it.
 struct KeptTranscript {
     int status = 0;        // PBCCS_OK / PBCCS_EINVAL / PBCCS_EOOM
@@ -137,6 +147,14 @@ public:
     void RunBanded(const AlignScoring& p, const PairView* pairs, int n, PairResult* out, const BandOptions& band,
                    BandInfo* info);
 
+    // The ends-free modes of the int32 aligner (mode kEndsSemiglobal / kEndsLocal; p.kind is kNw, Insert and Delete
+    // <= 0): the reference POA's rules on the target as one unbranched path.  Sorting, the rows per lane, the launch
+    // groups and PBCCS_EOOM are Run's.  out[k].transcript covers the extent ext[k]; out[k].scoreI is the end cell's
+    // score.  bothStrands: the query is also aligned reverse complemented and forward wins iff its score >= the
+    // other's.
+    void RunEnds(const AlignScoring& p, int mode, bool bothStrands, const PairView* pairs, int n, PairResult* out,
+                 EndsExtent* ext);
+
     AlignStats stats;
     AlignBandStats bandStats;
     bool profiling = false;
@@ -153,7 +171,7 @@ private:
     DevVec<uint8_t> dSeq_, dStore_, dOut_;
     DevVec<AlignJob> dJobs_;
     DevVec<AlignBandJob> dBandJobs_;
-    DevVec<int> dList_, dLens_, dStatus_;
+    DevVec<int> dList_, dLens_, dStatus_, dEnds_;
     DevVec<uint32_t> dCarry_, dScores_;
 };
 

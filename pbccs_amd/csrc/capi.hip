@@ -2950,6 +2950,65 @@ int pbccs_align_batch_ex(pbccs_engine* eng, const pbccs_align_params* params, co
     });
 }
 
+// the ends-free modes (align_modes_kernels.hip)
+int pbccs_align_batch_ends(pbccs_engine* eng, const pbccs_align_params* params, const pbccs_align_ends* ends,
+                           const pbccs_align_pair* pairs, int n, pbccs_align_result* out, pbccs_align_extent* ext)
+{
+    if (!eng || !params || !ends || n < 0 || (n > 0 && (!pairs || !out || !ext)))
+        return fail(PBCCS_EINVAL, "bad argument");
+    const pbccs_align_params& a = *params;
+    if (a.kind != PBCCS_ALIGN_NW)
+        return fail(PBCCS_EINVAL, "SEMIGLOBAL and LOCAL alignment are defined for the linear (NW) scores only");
+    if (ends->mode == PBCCS_POA_GLOBAL) return fail(PBCCS_EINVAL, "GLOBAL alignment is pbccs_align_batch's");
+    if (ends->mode != PBCCS_POA_SEMIGLOBAL && ends->mode != PBCCS_POA_LOCAL)
+        return fail(PBCCS_EINVAL, "unknown alignment mode");
+    if (a.insert > 0 || a.delete_ > 0)
+        return fail(PBCCS_EINVAL, "SEMIGLOBAL and LOCAL alignment need Insert <= 0 and Delete <= 0");
+    for (int k = 0; k < n; ++k) {
+        const pbccs_align_pair& p = pairs[k];
+        if (p.target_len < 0 || p.query_len < 0 || (p.target_len > 0 && !p.target) || (p.query_len > 0 && !p.query))
+            return fail(PBCCS_EINVAL, "bad pbccs_align_pair");
+        if (out[k].cap < 0 || (out[k].cap > 0 && !out[k].transcript)) return fail(PBCCS_EINVAL, "bad pbccs_align_result");
+    }
+    return guarded([&] {
+        const align::AlignScoring sc{align::kNw, a.match, a.mismatch, a.insert, a.delete_, 0.f, 0.f, 0.f, 0.f, 0.f};
+        std::vector<align::PairView> pv(n);
+        for (int k = 0; k < n; ++k) pv[k] = align::PairView{pairs[k].target, pairs[k].target_len, pairs[k].query, pairs[k].query_len};
+        std::vector<align::PairResult> res(n);
+        std::vector<align::EndsExtent> ex(n);
+        {
+            std::lock_guard<std::mutex> lk(eng->alignMu);
+            eng->Align().RunEnds(sc, ends->mode, ends->both_strands != 0, pv.data(), n, res.data(), ex.data());
+        }
+        int rc = PBCCS_OK;
+        bool small = false;
+        for (int k = 0; k < n; ++k) {
+            pbccs_align_result& o = out[k];
+            const align::PairResult& r = res[k];
+            o.len = (int)r.transcript.size();
+            o.score_i = r.scoreI;
+            o.score_f = 0.f;
+            o.status = r.status;
+            ext[k] = pbccs_align_extent{ex[k].targetBegin, ex[k].targetEnd, ex[k].queryBegin, ex[k].queryEnd, ex[k].rc};
+            if (r.status != PBCCS_OK) {
+                if (rc == PBCCS_OK) rc = r.status;
+                continue;
+            }
+            if (o.len > o.cap) {
+                o.status = PBCCS_ERANGE;
+                small = true;
+                continue;
+            }
+            if (o.len > 0) std::memcpy(o.transcript, r.transcript.data(), (size_t)o.len);
+        }
+        if (rc == PBCCS_EINVAL) return fail(rc, "a pair cannot be aligned (int32 overflow)");
+        if (rc == PBCCS_EOOM) return fail(rc, "a pair's move store exceeds the align workspace (PBCCS_ALIGN_WORKSPACE_MB)");
+        if (rc != PBCCS_OK) return fail(rc, "alignment failed");
+        if (small) return fail(PBCCS_ERANGE, "transcript buffer too small");
+        return PBCCS_OK;
+    });
+}
+
 int pbccs_align_stats_get(pbccs_engine* eng, pbccs_align_stats* out, int reset)
 {
     if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");

@@ -199,6 +199,15 @@ class CAlignBandStats(ctypes.Structure):
                 ("store_bytes", ctypes.c_double), ("fill_ms", ctypes.c_double), ("trace_ms", ctypes.c_double)]
 
 
+class CAlignEnds(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("both_strands", ctypes.c_int)]
+
+
+class CAlignExtent(ctypes.Structure):
+    _fields_ = [("target_begin", ctypes.c_int), ("target_end", ctypes.c_int), ("query_begin", ctypes.c_int),
+                ("query_end", ctypes.c_int), ("rc", ctypes.c_int)]
+
+
 class CMapInput(ctypes.Structure):
     _fields_ = [("draft", ctypes.c_char_p), ("draft_len", ctypes.c_int), ("seqs", ctypes.POINTER(ctypes.c_char_p)),
                 ("lens", ctypes.POINTER(ctypes.c_int)), ("n_reads", ctypes.c_int)]
@@ -520,6 +529,10 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_double), PI]),
     "pbccs_align_band_widen": (I, [ctypes.POINTER(CAlignParams), I, I, ctypes.c_double, PI]),
     "pbccs_align_band_stats_get": (I, [P, ctypes.POINTER(CAlignBandStats), I]),
+    # the ends-free modes
+    "pbccs_align_batch_ends": (I, [P, ctypes.POINTER(CAlignParams), ctypes.POINTER(CAlignEnds),
+                                   ctypes.POINTER(CAlignPair), I, ctypes.POINTER(CAlignResult),
+                                   ctypes.POINTER(CAlignExtent)]),
     "pbccs_ccs_batch": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.c_longlong, ctypes.POINTER(CPolishOptions),
                             ctypes.POINTER(CCcsOutput)]),
     # MapToDraft and the capped ccs that keeps every pass

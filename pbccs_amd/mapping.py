@@ -18,10 +18,34 @@ def _engine(engine):
     return engine
 
 
-def map_batch(zmws, min_score_to_add=0.0, engine=None):
+MAP_PARAMS = (3, -5, -4, -4)   # DefaultPoaConfig's Match, Mismatch, Insert, Delete: k_map_fill's scores
+
+
+def _add_transcripts(zmws, res, eng):
+    """map_batch(transcripts=True): the path of every mapped read, from one LOCAL call of the ends-free aligner
+    (align.align_ends_batch) with the mapper's scores on the read in the orientation the mapper
+    chose.  Same rules, same ties, so the path covers the summary's own extents."""
+    from . import align as A
+    pairs, where = [], []
+    for z, (draft, reads) in enumerate(zmws):
+        for k, r in enumerate(reads):
+            m = res[z][k]
+            if m is not None:
+                pairs.append((draft, A.reverse_complement(r) if m["rc"] else r))
+                where.append(m)
+    if not pairs:
+        return
+    alns, _, _ = A.align_ends_batch(pairs, A.LOCAL, A.AlignParams(*MAP_PARAMS), engine=eng)
+    for m, a in zip(where, alns):
+        m["transcript"] = a.Transcript()
+
+
+def map_batch(zmws, min_score_to_add=0.0, engine=None, transcripts=False):
     """zmws: [(draft, [read or None, ...])].  Returns per ZMW a list with one entry per read: None for a read that
     was not mapped (no read, or both orientations below min_score_to_add), else {"rc", "read": (b, e), "tpl":
     (b, e), "score"} -- the PoaAlignmentSummary driver.extract_mapped_read takes, plus the alignment score.
+    transcripts=True adds "transcript" to each summary: the LOCAL path (M R I D, draft as target) over
+    draft[tpl] and the oriented read[read], from a second device call (_add_transcripts).
 
     Marshalling is flat, as poa.poa_batch's: all sequences in one buffer with a pointer table, all outputs in
     shared arrays, the per-ZMW structs written column-wise."""
@@ -71,13 +95,15 @@ def map_batch(zmws, min_score_to_add=0.0, engine=None):
         res.append([{"rc": bool(rc_l[k]), "read": (ext_l[4 * k], ext_l[4 * k + 1]),
                      "tpl": (ext_l[4 * k + 2], ext_l[4 * k + 3]), "score": sc_l[k]} if m_l[k] else None
                     for k in range(f, f + cnts[z])])
+    if transcripts:
+        _add_transcripts(zmws, res, eng)
     return res
 
 
-def map_to_draft(draft, reads, min_score_to_add=0.0, engine=None):
+def map_to_draft(draft, reads, min_score_to_add=0.0, engine=None, transcripts=False):
     """MapToDraft(draft, reads, minScoreToAdd): one entry per read, None when it was not mapped, else the summary
-    {"rc", "read", "tpl", "score"}."""
-    return map_batch([(draft, list(reads))], min_score_to_add, engine)[0]
+    {"rc", "read", "tpl", "score"} (and "transcript" with transcripts=True, see map_batch)."""
+    return map_batch([(draft, list(reads))], min_score_to_add, engine, transcripts)[0]
 
 
 def map_stats(engine=None, reset=False):
