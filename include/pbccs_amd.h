@@ -1451,6 +1451,90 @@ int pbccs_ccs_batch_split(pbccs_engine* eng, const pbccs_ccs_input* in, int n, c
                           const pbccs_polish_extras* extras, const pbccs_split_options* split,
                           pbccs_ccs_split_output* split_out, pbccs_ccs_output* out);
 
+/* ---- barcode demultiplexing ---------------------------------------------------------------
+ * Which barcode pair flanks a CCS read.  The reference has no demultiplexing; the rules are this project's own,
+ * built from pbccs_align_batch_ends' SEMIGLOBAL rules, and tests/demux_restatement.py states them in full.
+ *
+ * W = window, or window_mult (<= 0: 3) times the longest barcode when window <= 0; 1 <= W <= 1024.  A read of
+ * length n has the leading window [0, min(W, n)) and the trailing window [off, n), off = max(0, n - W).  lead[b] is
+ * the SEMIGLOBAL score of barcode b (the query) inside the leading window (the target), trail[b] that of its reverse
+ * complement inside the trailing window; read bytes are raw, a byte that is not exactly a barcode's byte matches
+ * nothing.  An empty (or NULL) read launches nothing and scores len(b) * Insert on both ends.  Per end, best is the
+ * smallest index holding the maximum and second the maximum over every other index (INT_MIN with one barcode).
+ * Asymmetric design: i = best of lead, j = best of trail, score = lead[i] + trail[j], score_lead = the smaller of the
+ * two ends' best - second.  Symmetric design: i = j = the best of lead + trail, score and score_lead from that sum.
+ * A lead with no second is INT_MAX.  quality = clamp(floor(100 * score / (Match * (len_i + len_j))), 0, 100); the
+ * read is called iff quality >= min_quality and score_lead >= min_score_lead.  The extents are the target extents of
+ * the two called barcodes' alignments in read coordinates, as pbccs_align_batch_ends reports them. */
+#define PBCCS_DEMUX_MIN_QUALITY 74   /* the midpoint of the measured null (64) and planted (84) qualities, §3.27 */
+#define PBCCS_DEMUX_MAX_BARCODES 65535
+#define PBCCS_DEMUX_MAX_BARCODE_LEN 64
+#define PBCCS_DEMUX_MAX_WINDOW 1024
+#define PBCCS_DEMUX_ASYMMETRIC 0
+#define PBCCS_DEMUX_SYMMETRIC 1
+
+typedef struct {
+    const char* const* seqs;   /* n barcodes, each 1..64 bases of uppercase ACGT */
+    const int* lens;
+    int n;                     /* 1..65535 */
+} pbccs_demux_barcodes;
+
+typedef struct {
+    int match, mismatch, insert, delete_;   /* Match > 0, Insert <= 0, Delete <= 0 */
+    int design;                             /* PBCCS_DEMUX_ASYMMETRIC / PBCCS_DEMUX_SYMMETRIC */
+    int window;                             /* <= 0: window_mult times the longest barcode */
+    int window_mult;                        /* <= 0: 3 */
+    int min_quality;                        /* < 0: PBCCS_DEMUX_MIN_QUALITY */
+    int min_score_lead;
+} pbccs_demux_options;
+/* (3, -5, -4, -4), asymmetric, window 0, window_mult 3, min_quality PBCCS_DEMUX_MIN_QUALITY, min_score_lead 0 */
+void pbccs_demux_options_default(pbccs_demux_options* o);
+
+typedef struct {
+    const char* seq;   /* may be NULL when len is 0 */
+    int len;
+} pbccs_demux_read;
+
+/* Every array may be NULL; each holds one entry per read unless it says otherwise. */
+typedef struct {
+    int* lead;          /* the called barcodes i and j; filled for an uncalled read too */
+    int* trail;
+    int* called;        /* 1 / 0; the reported pair of an uncalled read is (-1, -1) */
+    int* score;
+    int* score_lead;
+    int* quality;
+    int* extents;       /* 4 per read: leading begin, end, trailing begin, end, in read coordinates */
+    int* clip;          /* 2 per read: leading end, trailing begin; (-1, -1) when they cross */
+    int* overlap;       /* 1 when leading end > trailing begin (the windows overlapped on a short read) */
+    int* best;          /* 6 per read: leading best score, its index, second; the same for the trailing end */
+    int* scores;        /* n * 2 * B: the full score matrix, [read][end][barcode] */
+} pbccs_demux_output;
+
+/* PBCCS_EINVAL before any device work: a bad barcode set (count, length, a byte that is not A C G T), Match <= 0,
+ * Insert > 0, Delete > 0, an unknown design, W outside 1..1024, a negative read length, a NULL read with a positive
+ * length, or scores that could leave int32: 2 * (longest barcode + W) * the largest |score| above INT_MAX
+ * (pbccs_align_batch's rule applied to the sum of the two ends).  The batch is split into launches whose windows and
+ * score rows fit PBCCS_DEMUX_WORKSPACE_KB (default 262144); a launch holds at least one read. */
+int pbccs_demux_batch(pbccs_engine* eng, const pbccs_demux_barcodes* barcodes, const pbccs_demux_options* opts,
+                      const pbccs_demux_read* reads, int n, pbccs_demux_output* out);
+
+/* Demultiplexing work since the last reset: reads given, DP cells (2 * min(W, n) * the sum of the barcode lengths
+ * per read that reached the device), kernel launches, device ms (profiling on). */
+typedef struct {
+    long long reads, cells, launches;
+    double device_ms;
+} pbccs_demux_stats;
+int pbccs_demux_stats_get(pbccs_engine* eng, pbccs_demux_stats* out, int reset);
+
+/* pbccs_ccs_batch followed by one pbccs_demux_batch over the consensuses of the ZMWs that ended Success.  demux
+ * holds one entry per ZMW (entry z of every array belongs to ZMW z; scores must be NULL); demuxed_mask[z], when not
+ * NULL, is 1 for the ZMWs that were demultiplexed and 0 for the others, whose entries are left untouched.  The
+ * barcodes and options are refused before any device work. */
+int pbccs_ccs_batch_demux(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
+                          const pbccs_polish_options* opts, const pbccs_demux_barcodes* barcodes,
+                          const pbccs_demux_options* demux_opts, pbccs_ccs_output* out, pbccs_demux_output* demux,
+                          int* demuxed_mask);
+
 #ifdef __cplusplus
 }
 #endif

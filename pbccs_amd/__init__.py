@@ -387,6 +387,7 @@ from .strand import StrandSite, StrandSums, strand_stats  # noqa: E402,F401
 from .kinetics import (codec_v1_decode, codec_v1_encode, kinetics_batch, kinetics_pileup,  # noqa: E402,F401
                        kinetics_stats)
 from .pileup import pileup_batch, pileup_columns, pileup_msa, pileup_stats  # noqa: E402,F401
+from .demux import BarcodeSet, clip_read, demux_batch, demux_stats  # noqa: E402,F401
 
 __all__ = [
     "ArrowConfig", "ArrowMultiReadMutationScorer", "ConsensusQVs", "ConsensusSettings", "Engine", "Mutation",

@@ -148,7 +148,7 @@ def _ccs_name(movie, hole, strand):
     return f"{movie}/{hole}/ccs/{strand}"
 
 
-def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=None, pileup=False):
+def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=None, pileup=False, barcode=False):
     """The CCS record of src/main/ccs.cpp:105-172 as a SAM text line (unmapped, flag 4; MAPQ 255).
 
     result: one pbccs_amd polish result (status Success).  Tags in the reference's order: RG zm np rq sn pq
@@ -164,9 +164,29 @@ def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=
     is named movie/hole/ccs/fwd or .../ccs/rev.
     pileup=True (a result made with pileup=True): the effective coverage follows every other tag as ec:f: (the sum
     over the consensus of the subread columns standing on each position, over its length).
+    barcode=True (a result made with barcodes=): a called read's barcode pair and quality follow
+    every other tag as bc:B:S,<min>,<max> and bq:i:<quality>; an uncalled read gets neither.  barcode="clip" also
+    trims SEQ and QUAL to the insert, read[clip[0]:clip[1]], and appends bx:B:i,<leading bases removed>,<trailing
+    bases removed>; a read whose two barcodes overlap is written whole, with bx:B:i,0,0.  The per-base tags are not
+    trimmed, so "clip" with rich, kinetics or pileup raises UnsupportedFeatureError.  The tag names follow PacBio's
+    BAM convention as published; they are restated and unpinned, as the kinetics codec is.
     """
+    if barcode not in (False, True, "clip"):
+        raise ValueError('barcode: False, True or "clip"')
+    if barcode == "clip" and (rich or kinetics or pileup):
+        from .align import UnsupportedFeatureError
+        raise UnsupportedFeatureError('barcode="clip" does not trim the per-base tags of rich, kinetics or pileup')
     name = _ccs_name(movie, hole, strand)
     qual = QVsToASCII(result["qvs"])
+    seq = result["consensus"]
+    bc_tags = []
+    entry = result.get("barcode") if barcode else None
+    if entry is not None and entry["called"]:
+        bc_tags = [f"bc:B:S,{int(entry['pair'][0])},{int(entry['pair'][1])}", f"bq:i:{int(entry['quality'])}"]
+        if barcode == "clip":
+            b, e = (0, len(seq)) if entry["clip"] is None else entry["clip"]
+            bc_tags.append(f"bx:B:i,{int(b)},{len(seq) - int(e)}")
+            seq, qual = seq[b:e], qual[b:e]
     # zs: ZScores().second -- one entry per read the scorer took (inactive ones NaN), in AddRead order
     # (MultiReadMutationScorer.hpp:208-260).  ccs_batch results index their per-read arrays by subread and carry
     # that order ("add_order": FilterReads' stable sort, Consensus.h:281); polish results are in AddRead order.
@@ -190,8 +210,8 @@ def ccs_sam_record(movie, hole, result, snr, rich=False, kinetics=False, strand=
                  codes("ri", "rev_ipd"), codes("rp", "rev_pw"), f"rn:i:{int(result['rn'])}"]
     if pileup:
         tags.append(f"ec:f:{_f32(result['ec'])}")
-    fields =[name, "4", "*", "0", "255", "*", "*", "0", "0", result["consensus"] or "*", qual or "*"]
-    return "\t".join(fields + tags)
+    fields =[name, "4", "*", "0", "255", "*", "*", "0", "0", seq or "*", qual or "*"]
+    return "\t".join(fields + tags + bc_tags)
 
 
 _COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}

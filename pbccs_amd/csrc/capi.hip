@@ -29,6 +29,7 @@
 #include "kinetics_kernels.hpp"
 #include "pileup_kernels.hpp"
 #include "map_kernels.hpp"
+#include "demux_kernels.hpp"
 #include "split_map_kernels.hpp"
 #include "poa_engine.hpp"
 #include "quiver_engine.hpp"
@@ -157,6 +158,15 @@ struct pbccs_engine {
         if (!pileupRunner) pileupRunner.reset(new pileup::PileupRunner(device));
         pileupRunner->profiling = profiling;
         return *pileupRunner;
+    }
+    // the demultiplexer's workspace (made on first use): its own stream; calls on one engine take turns on it
+    std::unique_ptr<demux::DemuxRunner> demuxRunner;
+    std::mutex demuxMu;
+    demux::DemuxRunner& Demux()
+    {
+        if (!demuxRunner) demuxRunner.reset(new demux::DemuxRunner(device));
+        demuxRunner->profiling = profiling;
+        return *demuxRunner;
     }
     Workspace* Slot(int s)
     {
@@ -5103,6 +5113,159 @@ int pbccs_ccs_batch_split(pbccs_engine* eng, const pbccs_ccs_input* in, int n, c
     if (so.max_segments > map::kSplitMaxSegments) return fail(PBCCS_EINVAL, "max_segments above 64");
     return ccs_batch_impl(eng, in, n, c.max_poa_coverage, c.map_past_cap != 0, poa && poa->banded != 0, opts, out,
                           nullptr, nullptr, extras ? extras->rich : nullptr, nullptr, nullptr, &so, split_out);
+}
+
+// ---- barcode demultiplexing (demux_kernels.hpp) -------------------------------------------------------------
+void pbccs_demux_options_default(pbccs_demux_options* o)
+{
+    if (!o) return;
+    *o = pbccs_demux_options{3, -5, -4, -4, PBCCS_DEMUX_ASYMMETRIC, 0, 3, PBCCS_DEMUX_MIN_QUALITY, 0};
+}
+
+namespace {
+// The refusals of pbccs_demux_batch that need no read: PBCCS_OK, or the failure already recorded.  *o receives the
+// resolved options (the window, the design, the thresholds).
+int demux_check(const pbccs_demux_barcodes* bc, const pbccs_demux_options* opts, demux::DemuxOptions* o)
+{
+    if (!bc || !bc->seqs || !bc->lens) return fail(PBCCS_EINVAL, "bad pbccs_demux_barcodes");
+    if (bc->n < 1 || bc->n > PBCCS_DEMUX_MAX_BARCODES) return fail(PBCCS_EINVAL, "1 to 65535 barcodes");
+    int longest = 0;
+    for (int b = 0; b < bc->n; ++b) {
+        const int len = bc->lens[b];
+        if (len < 1 || len > PBCCS_DEMUX_MAX_BARCODE_LEN || !bc->seqs[b])
+            return fail(PBCCS_EINVAL, "a barcode has 1 to 64 bases");
+        for (int k = 0; k < len; ++k) {
+            const char c = bc->seqs[b][k];
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T')
+                return fail(PBCCS_EINVAL, "a barcode holds uppercase A, C, G and T only");
+        }
+        longest = std::max(longest, len);
+    }
+    pbccs_demux_options d;
+    pbccs_demux_options_default(&d);
+    if (opts) d = *opts;
+    if (d.match <= 0 || d.insert > 0 || d.delete_ > 0)
+        return fail(PBCCS_EINVAL, "demux needs Match > 0, Insert <= 0 and Delete <= 0");
+    if (d.design != PBCCS_DEMUX_ASYMMETRIC && d.design != PBCCS_DEMUX_SYMMETRIC)
+        return fail(PBCCS_EINVAL, "unknown demux design");
+    const long long W = d.window > 0 ? d.window : (long long)(d.window_mult > 0 ? d.window_mult : 3) * longest;
+    if (W < 1 || W > PBCCS_DEMUX_MAX_WINDOW) return fail(PBCCS_EINVAL, "the demux window is 1 to 1024 bases");
+    const long long mx = std::max(std::max(std::llabs((long long)d.match), std::llabs((long long)d.mismatch)),
+                                  std::max(std::llabs((long long)d.insert), std::llabs((long long)d.delete_)));
+    if (2 * (longest + W) * mx > 0x7fffffffLL) return fail(PBCCS_EINVAL, "demux scores could leave int32");
+    o->match = d.match;
+    o->mismatch = d.mismatch;
+    o->insert = d.insert;
+    o->delete_ = d.delete_;
+    o->symmetric = d.design == PBCCS_DEMUX_SYMMETRIC;
+    o->window = (int)W;
+    o->minQuality = d.min_quality < 0 ? PBCCS_DEMUX_MIN_QUALITY : d.min_quality;
+    o->minScoreLead = d.min_score_lead;
+    return PBCCS_OK;
+}
+
+// Runs the checked call and writes entry k of the device's answer to entry at[k] of the caller's arrays (at NULL:
+// entry k).  scores only with at NULL.
+void demux_run(pbccs_engine* eng, const pbccs_demux_barcodes* bc, const demux::DemuxOptions& o,
+               const std::vector<const char*>& seqs, const std::vector<int>& lens, const int* at,
+               pbccs_demux_output* out)
+{
+    const int n = (int)seqs.size();
+    std::vector<demux::DemuxEnd> ends((size_t)2 * n);
+    std::vector<demux::DemuxCall> calls((size_t)n);
+    {
+        std::lock_guard<std::mutex> lk(eng->demuxMu);
+        eng->Demux().Run(bc->seqs, bc->lens, bc->n, o, seqs.data(), lens.data(), n, ends.data(), calls.data(),
+                         at ? nullptr : out->scores);
+    }
+    for (int k = 0; k < n; ++k) {
+        const size_t r = at ? (size_t)at[k] : (size_t)k;
+        const demux::DemuxCall& c = calls[k];
+        if (out->lead) out->lead[r] = c.lead;
+        if (out->trail) out->trail[r] = c.trail;
+        if (out->called) out->called[r] = c.called;
+        if (out->score) out->score[r] = c.score;
+        if (out->score_lead) out->score_lead[r] = c.scoreLead;
+        if (out->quality) out->quality[r] = c.quality;
+        if (out->extents) {
+            const int v[4] = {c.leadBegin, c.leadEnd, c.trailBegin, c.trailEnd};
+            std::copy(v, v + 4, out->extents + 4 * r);
+        }
+        const bool over = c.leadEnd > c.trailBegin;
+        if (out->clip) {
+            out->clip[2 * r] = over ? -1 : c.leadEnd;
+            out->clip[2 * r + 1] = over ? -1 : c.trailBegin;
+        }
+        if (out->overlap) out->overlap[r] = over ? 1 : 0;
+        if (out->best)
+            for (int e = 0; e < 2; ++e) {
+                const demux::DemuxEnd& x = ends[(size_t)2 * k + e];
+                const int v[3] = {x.best, x.index, x.second};
+                std::copy(v, v + 3, out->best + 6 * r + 3 * e);
+            }
+    }
+}
+}  // namespace
+
+int pbccs_demux_batch(pbccs_engine* eng, const pbccs_demux_barcodes* barcodes, const pbccs_demux_options* opts,
+                      const pbccs_demux_read* reads, int n, pbccs_demux_output* out)
+{
+    if (!eng || n < 0 || (n > 0 && (!reads || !out))) return fail(PBCCS_EINVAL, "bad argument");
+    demux::DemuxOptions o;
+    if (const int rc = demux_check(barcodes, opts, &o)) return rc;
+    for (int r = 0; r < n; ++r)
+        if (reads[r].len < 0 || (reads[r].len > 0 && !reads[r].seq))
+            return fail(PBCCS_EINVAL, "bad read (NULL sequence or negative length)");
+    if (n == 0) return PBCCS_OK;
+    return guarded([&] {
+        std::vector<const char*> seqs(n);
+        std::vector<int> lens(n);
+        for (int r = 0; r < n; ++r) {
+            seqs[r] = reads[r].seq;
+            lens[r] = reads[r].len;
+        }
+        demux_run(eng, barcodes, o, seqs, lens, nullptr, out);
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_demux_stats_get(pbccs_engine* eng, pbccs_demux_stats* out, int reset)
+{
+    if (!eng || !out) return fail(PBCCS_EINVAL, "bad argument");
+    return guarded([&] {
+        std::lock_guard<std::mutex> lk(eng->demuxMu);
+        const demux::DemuxStats s = eng->demuxRunner ? eng->demuxRunner->stats : demux::DemuxStats();
+        *out = pbccs_demux_stats{s.reads, s.cells, s.launches, s.deviceMs};
+        if (reset && eng->demuxRunner) eng->demuxRunner->stats = demux::DemuxStats();
+        return PBCCS_OK;
+    });
+}
+
+int pbccs_ccs_batch_demux(pbccs_engine* eng, const pbccs_ccs_input* in, int n, long long max_poa_coverage,
+                          const pbccs_polish_options* opts, const pbccs_demux_barcodes* barcodes,
+                          const pbccs_demux_options* demux_opts, pbccs_ccs_output* out, pbccs_demux_output* demux,
+                          int* demuxed_mask)
+{
+    if (!eng || (n > 0 && !demux)) return fail(PBCCS_EINVAL, "bad argument");
+    if (demux && demux->scores) return fail(PBCCS_EINVAL, "pbccs_ccs_batch_demux returns no score matrix");
+    demux::DemuxOptions o;
+    if (const int rc = demux_check(barcodes, demux_opts, &o)) return rc;
+    const int rc = pbccs_ccs_batch(eng, in, n, max_poa_coverage, opts, out);
+    if (rc != PBCCS_OK) return rc;
+    return guarded([&] {
+        std::vector<const char*> seqs;
+        std::vector<int> lens, at;
+        for (int z = 0; z < n; ++z) {
+            const bool ok = out[z].polish.status == 0 && out[z].polish.consensus && out[z].polish.consensus_len > 0;
+            if (demuxed_mask) demuxed_mask[z] = ok ? 1 : 0;
+            if (!ok) continue;
+            seqs.push_back(out[z].polish.consensus);
+            lens.push_back(out[z].polish.consensus_len);
+            at.push_back(z);
+        }
+        if (!seqs.empty()) demux_run(eng, barcodes, o, seqs, lens, at.data(), demux);
+        return PBCCS_OK;
+    });
 }
 
 }  // extern "C"

@@ -277,7 +277,7 @@ def zmw_inputs_batch(chunks, min_length=10, max_poa_coverage=None, engine=None, 
 
 def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_past_cap=False, banded_poa=False,
               polish_window=None, rich_qvs=False, kinetics=False, strand_sites=False, directional=None,
-              pileup=False, split_long_reads=False):
+              pileup=False, split_long_reads=False, barcodes=None):
     """Consensus.h's per-ZMW driver for many ZMWs in one native call (pbccs_ccs_batch): FilterReads,
     the GPU POA, TooShort, ExtractMappedRead and the GPU polish, with no Python between the stages.
     chunks: [{"snr", "reads": [{"seq", "flags"?}]}].  Returns per ZMW the polish result dict (as
@@ -319,6 +319,11 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
     "add_read_result", "zscore"}]}] and "n_missed_adapters" (the sum of the chains' segments - 1); the subread's
     own add_read_results / zscores entries stay -1 / NaN (so kinetics and pileup leave it out), and "add_order"
     repeats its index once per added segment.  Not with polish_window, strand_sites or directional (ValueError).
+    barcodes (pbccs_ccs_batch_demux, or pbccs_demux_batch after the native call of the other options; DESIGN.md
+    §3.27): None, a demux.BarcodeSet, or a dict with "barcodes" and any of demux.demux_batch's keywords (params,
+    design, window, window_mult, min_quality, min_score_lead).  Every ZMW that ended Success also carries "barcode",
+    what demux.demux_batch returns for its consensus; all of them are demultiplexed in one native call.  A bad set
+    or option raises before any device work.
     Raises on a draft longer than its buffer (PBCCS_ERANGE).
 
     Marshalling is flat, as poa.poa_batch's: every subread in one buffer behind one pointer table, every
@@ -351,6 +356,10 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         pile_opts = {} if pileup is True else pileup
         if not isinstance(pile_opts, dict) or set(pile_opts) - {"msa", "transcripts", "band", "arrays"}:
             raise ValueError('ccs_batch(pileup=...): True, or a dict with any of "msa", "transcripts", "band", "arrays"')
+    demux_spec = demux_native = None
+    if barcodes is not None:   # before any engine is touched
+        from .demux import demux_options
+        demux_spec = demux_options(barcodes)
     eng = engine or default_engine()
     settings = settings or ConsensusSettings()
     n = len(chunks)
@@ -490,6 +499,19 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
         L.check(L.load().pbccs_ccs_batch_ex(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
                                             ctypes.byref(co), ctypes.byref(opts),
                                             ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput))))
+    elif demux_spec is not None:   # the plain call and the demultiplexing of its Success consensuses, natively
+        from . import demux as _demux
+        dout, darrs = _demux._outputs(n)
+        dmask = np.zeros(max(1, n), dtype=np.int32)
+        bset, keep = demux_spec[0]._c()
+        L.check(L.load().pbccs_ccs_batch_demux(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n,
+                                               mc, ctypes.byref(opts), ctypes.byref(bset),
+                                               ctypes.byref(demux_spec[2]),
+                                               ctypes.cast(outs.ctypes.data, ctypes.POINTER(L.CCcsOutput)),
+                                               ctypes.byref(dout),
+                                               ctypes.cast(dmask.ctypes.data, ctypes.POINTER(ctypes.c_int))))
+        del keep
+        demux_native = (_demux._entries(n, darrs), dmask.tolist())
     else:
         L.check(L.load().pbccs_ccs_batch(eng._h, ctypes.cast(ins.ctypes.data, ctypes.POINTER(L.CCcsInput)), n, mc,
                                          ctypes.byref(opts),
@@ -561,4 +583,14 @@ def ccs_batch(chunks, settings=None, engine=None, max_poa_coverage=None, map_pas
             for z, g in zip(todo, piles):
                 res[z]["pileup"] = g
                 res[z]["ec"] = g["ec"]
+    if demux_native is not None:
+        for z in range(n):
+            if demux_native[1][z]:
+                res[z]["barcode"] = demux_native[0][z]
+    elif demux_spec is not None:   # beside the other options: one more native call, after theirs
+        from .demux import demux_batch
+        todo = [z for z in range(n) if res[z]["status_code"] == 0 and res[z]["consensus"]]
+        got = demux_batch([res[z]["consensus"] for z in todo], demux_spec[0], engine=eng, **demux_spec[1])
+        for z, g in zip(todo, got):
+            res[z]["barcode"] = g
     return res

@@ -407,6 +407,32 @@ class CPileupStats(ctypes.Structure):
                 ("reduce_ms", ctypes.c_double), ("scan_ms", ctypes.c_double), ("rows_ms", ctypes.c_double)]
 
 
+class CDemuxBarcodes(ctypes.Structure):
+    _fields_ = [("seqs", ctypes.POINTER(ctypes.c_char_p)), ("lens", ctypes.POINTER(ctypes.c_int)),
+                ("n", ctypes.c_int)]
+
+
+class CDemuxOptions(ctypes.Structure):
+    _fields_ = [("match", ctypes.c_int), ("mismatch", ctypes.c_int), ("insert", ctypes.c_int),
+                ("delete_", ctypes.c_int), ("design", ctypes.c_int), ("window", ctypes.c_int),
+                ("window_mult", ctypes.c_int), ("min_quality", ctypes.c_int), ("min_score_lead", ctypes.c_int)]
+
+
+class CDemuxRead(ctypes.Structure):
+    _fields_ = [("seq", ctypes.c_void_p), ("len", ctypes.c_int)]
+
+
+class CDemuxOutput(ctypes.Structure):
+    _fields_ = [(k, ctypes.POINTER(ctypes.c_int)) for k in
+                ("lead", "trail", "called", "score", "score_lead", "quality", "extents", "clip", "overlap", "best",
+                 "scores")]
+
+
+class CDemuxStats(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_longlong), ("cells", ctypes.c_longlong), ("launches", ctypes.c_longlong),
+                ("device_ms", ctypes.c_double)]
+
+
 # exported symbol -> (restype, argtypes); tests check that every symbol of include/pbccs_amd.h is exported
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -603,6 +629,14 @@ SIGNATURES = {
     "pbccs_pileup_msa": (I, [P, ctypes.POINTER(CPileupColumnsInput), I, PI, ctypes.POINTER(PI),
                              ctypes.POINTER(ctypes.c_char_p)]),
     "pbccs_pileup_stats_get": (I, [P, ctypes.POINTER(CPileupStats), I]),
+    # barcode demultiplexing
+    "pbccs_demux_options_default": (None, [ctypes.POINTER(CDemuxOptions)]),
+    "pbccs_demux_batch": (I, [P, ctypes.POINTER(CDemuxBarcodes), ctypes.POINTER(CDemuxOptions),
+                              ctypes.POINTER(CDemuxRead), I, ctypes.POINTER(CDemuxOutput)]),
+    "pbccs_demux_stats_get": (I, [P, ctypes.POINTER(CDemuxStats), I]),
+    "pbccs_ccs_batch_demux": (I, [P, ctypes.POINTER(CCcsInput), I, ctypes.c_longlong, ctypes.POINTER(CPolishOptions),
+                                  ctypes.POINTER(CDemuxBarcodes), ctypes.POINTER(CDemuxOptions),
+                                  ctypes.POINTER(CCcsOutput), ctypes.POINTER(CDemuxOutput), PI]),
 }
 # bound like the rest; kept apart because SIGNATURES is compared with the header's names of letters and underscores
 DIGIT_SIGNATURES = {

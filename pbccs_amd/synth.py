@@ -75,6 +75,28 @@ def make_fused_read(rng, truth, passes, read_errors=(0.07, 0.04, 0.01), first_st
     return {"seq": np.concatenate(parts).tobytes().decode(), "passes": where}
 
 
+def make_barcoded_zmw(rng, length, passes, barcodes, pair, snr=(10.0, 7.0, 5.0, 11.0),
+                      read_errors=(0.07, 0.04, 0.01)):
+    """make_zmw for a barcoded molecule: a random insert of `length` bases flanked by
+    barcodes[pair[0]] and the reverse complement of barcodes[pair[1]], before the draft and the passes are drawn.
+    Returns make_zmw's dict ("truth" is the flanked molecule) plus "insert" and "pair"."""
+    i, j = pair
+    insert = BASES[rng.integers(0, 4, size=length)]
+    lead = np.frombuffer(barcodes[i].encode(), dtype=np.uint8)
+    trail = COMP[np.frombuffer(barcodes[j].encode(), dtype=np.uint8)[::-1]]
+    truth = np.concatenate([lead, insert, trail])
+    draft = _mutate(rng, truth, 0.005, 0.005, 0.002)
+    reads = []
+    for k in range(passes):
+        r = _mutate(rng, truth, *read_errors)
+        strand = k % 2
+        if strand == 1:
+            r = COMP[r[::-1]]
+        reads.append({"seq": r.tobytes().decode(), "strand": strand, "ts": 0, "te": int(draft.shape[0])})
+    return {"truth": truth.tobytes().decode(), "insert": insert.tobytes().decode(), "pair": (int(i), int(j)),
+            "draft": draft.tobytes().decode(), "snr": list(snr), "reads": reads}
+
+
 def make_zmws(n, length, passes, seed, snr=(10.0, 7.0, 5.0, 11.0), length_range=None, passes_range=None,
               random_snr=False):
     """n ZMWs.  length_range/passes_range (inclusive) draw per-ZMW sizes (config #4)."""
